@@ -25,6 +25,15 @@ their own, reported as config.hit_gather (not part of `value`).
 Rank 0 at N=1 also times the CPU restatement (oracle/, the reference's
 algorithm restated in C++) on a bounded sample of the same reads on the host
 cores, and checks GPU == CPU hits on that sample.
+
+A plain run does only what `value` needs: it builds the index, simulates the
+reads and passes them through the FASTA ingest once (the timed call's input is
+that ingest's page-locked buffer), warms up, times the steps and prints the
+result line. Everything else above and below (the ingest timing, the device-resident pass,
+the counter runs and the roofline, the other PCIe-inclusive calls, the
+reference-execution pass, the full-size checks, the CPU baseline, the hit
+gather) runs under --full, where each part keeps its --no-... switch.
+--dump-outputs DIR writes the last timed step's hits (see dump_outputs).
 """
 from __future__ import annotations
 
@@ -102,6 +111,12 @@ def main():
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
     ap.add_argument("--reads", type=int, default=0, help="override reads per GPU")
     ap.add_argument("--ref-len", type=int, default=0, help="override reference length")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: ingest timing, device-resident pass, "
+                         "counters and roofline, the other PCIe-inclusive calls, reference-execution pass, full-size "
+                         "checks, CPU baseline, hit gather (each with its --no-... switch)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's hits as DIR/<name>.npy (float64)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU-baseline sample time")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-count", action="store_true", help="skip the instrumented (untimed) counter run")
@@ -123,6 +138,10 @@ def main():
                          "default profiles/traffic_<config>.json when it exists")
     args = ap.parse_args()
 
+    if not args.full:
+        if args.execution == "reference":
+            ap.error("--execution reference times the device-resident pass: it needs --full")
+        args.no_device_resident = args.no_gather = True
     if args.no_device_resident:
         if args.execution == "reference":
             ap.error("--execution reference times the device-resident pass: it cannot go with --no-device-resident")
@@ -166,17 +185,17 @@ def main():
     # distance and substitutions for Hamming (C2)
     reads, origin = sa.synth_reads(flat, lens, nreads, rlen, k if edit else 0, sigma=sigma, seed=7 + 1000003 * rank,
                                    substitutions=0 if edit else k, with_origin=True)
-    pats = sa.interleave_rc(reads, sigma)
+    pats = sa.interleave_rc(reads, sigma) if args.full else None  # the timed call interleaves on the device
     scheme = sa.search_scheme(gen, 0, k, rlen, hamming=not edit)
     log(f"rank {rank}: {nreads} reads simulated ({time.time()-t:.1f}s), {scheme[0].shape[0]} searches")
     # the timed call's input: the reads as `sahara search`'s FASTA ingest hands
     # them over — two bits per symbol in page-locked memory, N positions
     # listed (sahara_read_fasta form 2) — from the reads written as a FASTA
-    # file and read back, the ingest timed in both forms (--no-ingest: the
-    # library's packer fills the same form)
+    # file and read back, under --full with the ingest timed in both forms
+    # (--no-ingest: the library's packer fills the same form)
     ingest = None
     if not args.no_ingest:
-        ingest, packed = time_ingest(sa, reads, sigma)
+        ingest, packed = time_ingest(sa, reads, sigma, timed=args.full)
     else:
         packed = sa.pack_reads(reads, sigma, pinned=True)
     if args.execution == "reference":  # profiling aid: the timed steps are the reference's execution model
@@ -261,6 +280,8 @@ def main():
         digest = idx.digest()
     if args.execution == "reference":  # the timed steps are this mode's
         elapsed, step_stats, n_packed, packed_hits = dr_elapsed, dr_stats, nh, None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, packed_hits if packed_hits is not None else idx.fetch(), nreads)
 
     gather = None
     per_rank = None
@@ -562,7 +583,30 @@ def main():
         dist.destroy_process_group()
 
 
-def time_ingest(sa, reads, sigma):
+DUMP_READS = 500_000   # reads (of a seeded sample) whose hits --dump-outputs writes
+DUMP_ROWS = 1_900_000  # and at most this many hits: 4 float64 fields each, under 64 MB in all
+
+
+def dump_outputs(outdir, hits, nreads, seed=2024):
+    """What the timed call returned in its last step, as DIR/<name>.npy in
+    float64 (exact for every field): the hit records (qid, seq_id, pos, err;
+    canonical order) of a fixed, seeded sample of the reads, both strands,
+    cut to DUMP_ROWS rows, and n_hits = [hits of the whole call, hits of the
+    sampled reads]. The reads and the sample depend on the arguments alone,
+    so two builds are compared file by file."""
+    os.makedirs(outdir, exist_ok=True)
+    keep = np.zeros(nreads, bool)
+    keep[np.random.default_rng(seed).permutation(nreads)[:DUMP_READS]] = True
+    sel = hits[keep[(hits["qid"] >> np.uint64(1)).astype(np.int64)]]
+    n_sel = len(sel)
+    sel = sel[:DUMP_ROWS]
+    for name in ("qid", "seq_id", "pos", "err"):
+        np.save(os.path.join(outdir, name + ".npy"), sel[name].astype(np.float64))
+    np.save(os.path.join(outdir, "n_hits.npy"), np.array([len(hits), n_sel], np.float64))
+    log(f"outputs: {len(sel)} of {len(hits)} hits written to {outdir}")
+
+
+def time_ingest(sa, reads, sigma, timed=True):
     """The FASTA ingest that the timed region starts after, timed in both
     forms on the same reads written as a FASTA file (80 columns, one header
     per read, in /dev/shm when there is one): FASTA -> one rank per byte (the
@@ -570,7 +614,9 @@ def time_ingest(sa, reads, sigma):
     N list in page-locked memory (what `sahara search` hands to
     sahara_gpu_search_packed_compact), on the host threads the CLI uses.
     Returns the timings and the 2-bit form as PackedReads (checked against
-    the library's packer over the reads)."""
+    the library's packer over the reads). timed=False: the file is written
+    and read once in the 2-bit form, nothing is timed or checked, and the
+    timings are None."""
     import tempfile
     d = "/dev/shm" if os.path.isdir("/dev/shm") and os.access("/dev/shm", os.W_OK) else None
     n, m = reads.shape
@@ -597,6 +643,9 @@ def time_ingest(sa, reads, sigma):
         size = os.path.getsize(path)
         write_s = time.time() - t
         threads = host_threads()
+        if not timed:
+            r = sa.read_fasta(path, sigma, form=2, threads=threads)
+            return None, sa.PackedReads(r["data"], n, m, r["n_pos"])
         out = {"fasta_bytes": size, "threads": threads, "file": "tmpfs" if d else "tmp"}
         for form, name in ((1, "ranks"), (2, "two_bit")):
             best = None

@@ -136,6 +136,37 @@ def test_origin_recall():
     assert bench.origin_recall(moved, origin, 2) == pytest.approx(399 / 400)
 
 
+def test_dump_outputs_writes_a_fixed_sample(tmp_path, monkeypatch):
+    """bench.dump_outputs: float64 files of the hits of a seeded sample of the
+    reads (both strands, canonical order kept), the same sample on every call,
+    the totals beside them, and never more than DUMP_ROWS rows."""
+    monkeypatch.setattr(bench, "DUMP_READS", 40)
+    nreads = 100
+    rng = np.random.default_rng(1)
+    h = np.zeros(700, sa.HIT_DTYPE)
+    h["qid"] = np.sort(rng.integers(0, 2 * nreads, len(h), dtype=np.uint64))
+    h["seq_id"] = rng.integers(0, 24, len(h), dtype=np.uint32)
+    h["pos"] = rng.integers(0, 3_000_000_000, len(h), dtype=np.uint64)
+    h["err"] = rng.integers(0, 3, len(h), dtype=np.uint32)
+    a, b = tmp_path / "a", tmp_path / "b"
+    bench.dump_outputs(str(a), h, nreads)
+    bench.dump_outputs(str(b), h[h["qid"] != h["qid"][0]], nreads)  # another build losing one pattern's hits
+    got = {n: np.load(a / f"{n}.npy") for n in ("qid", "seq_id", "pos", "err", "n_hits")}
+    assert all(v.dtype == np.float64 for v in got.values())
+    reads = np.unique(got["qid"].astype(np.int64) >> 1)
+    assert 0 < len(reads) <= 40
+    sel = np.isin(h["qid"].astype(np.int64) >> 1, reads)
+    for n in ("qid", "seq_id", "pos", "err"):
+        assert np.array_equal(got[n], h[n][sel].astype(np.float64))
+    assert got["n_hits"].tolist() == [len(h), int(sel.sum())]
+    # the sample is of the reads, not of the rows: the other result's rows are this one's minus the lost ones
+    other = np.load(b / "qid.npy")
+    assert set(other.tolist()) <= set(got["qid"].tolist())
+    monkeypatch.setattr(bench, "DUMP_ROWS", 10)
+    bench.dump_outputs(str(a), h, nreads)
+    assert len(np.load(a / "pos.npy")) == 10 and np.load(a / "n_hits.npy").tolist() == [len(h), int(sel.sum())]
+
+
 def _mix64(x):
     M = (1 << 64) - 1
     x ^= x >> 30

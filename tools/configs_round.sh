@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$(realpath -m "$1"); shift
 mkdir -p "$OUT"
 for c in ${@:-c2 c5}; do
-  timeout -k 10 500 python3 "$R/bench.py" --config $c --no-cpu --no-ingest > "$OUT/$c.json" 2> "$OUT/$c.err" \
+  timeout -k 10 500 python3 "$R/bench.py" --full --config $c --no-cpu --no-ingest > "$OUT/$c.json" 2> "$OUT/$c.err" \
       || { echo "$c failed"; tail -5 "$OUT/$c.err"; exit 1; }
   python3 -c "
 import json,sys; d=json.load(open('$OUT/$c.json')); dr=d['config'].get('device_resident',{})

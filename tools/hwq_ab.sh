@@ -13,7 +13,7 @@ for q in 8 4; do
 done
 for i in 1 2; do
   for q in 8 4; do
-    GPU_MAX_HW_QUEUES=$q timeout -k 10 300 python3 -u bench.py --no-cpu > $OUT/bench_${q}_$i.txt 2>&1 || { tail -5 $OUT/bench_${q}_$i.txt; exit 1; }
+    GPU_MAX_HW_QUEUES=$q timeout -k 10 300 python3 -u bench.py --full --no-cpu > $OUT/bench_${q}_$i.txt 2>&1 || { tail -5 $OUT/bench_${q}_$i.txt; exit 1; }
     echo "bench hwq$q $i: $(tail -1 $OUT/bench_${q}_$i.txt | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); print(round(d["value"]/1e6,1), "M", d["ms_per_step"], "ms launch", d["roofline"]["launch_ms"])')" | tee -a $OUT/all.txt
   done
 done

@@ -14,6 +14,6 @@ i=0
 for grp in "${groups[@]}"; do
   i=$((i+1))
   timeout -k 10 300 rocprofv3 --pmc $grp --kernel-include-regex "${KREGEX:-kSearch}" -d "$OUT/pmc$i" -o run \
-      --output-format csv -- python3 "$R/bench.py" --no-cpu --no-count --warmup 0 --steps 1 "$@" \
+      --output-format csv -- python3 "$R/bench.py" --full --no-cpu --no-count --warmup 0 --steps 1 "$@" \
       > "$OUT/pmc$i.json" 2> "$OUT/pmc$i.err" || { echo "pass $i failed rc=$?"; exit 1; }
 done

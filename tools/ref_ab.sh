@@ -20,7 +20,7 @@ for i in $(seq 1 $N); do
       IFS=',' read -ra kv <<< "${S#*=}"
       envs+=("${kv[@]}")
     fi
-    env "${envs[@]}" timeout -k 10 400 python3 "$R/bench.py" --execution reference --no-cpu --no-e2e \
+    env "${envs[@]}" timeout -k 10 400 python3 "$R/bench.py" --full --execution reference --no-cpu --no-e2e \
         --no-verify --no-ingest "$@" > "$R/gpurun_out/ref_ab.json" 2> "$R/gpurun_out/ref_ab.log" \
       || { echo "FAIL $S"; tail -5 "$R/gpurun_out/ref_ab.log"; exit 1; }
     python3 -c "import json,sys; d=json.load(open('$R/gpurun_out/ref_ab.json')); print(sys.argv[1], round(d['value']/1e6,2), d['ms_per_step'])" "${S%%=*}"
