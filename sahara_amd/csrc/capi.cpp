@@ -177,40 +177,36 @@ Ctx* newCtx(int device) {
     if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos)
         throw Error(std::string("libsahara_hip is built for gfx950 (MI355X); device is ") + prop.gcnArchName);
     c->numCU = prop.multiProcessorCount;
-    SH_HIP(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
     // (No stream gets a CU mask: with a CU-masked stream in the process the
     // memory-bound kernels on the other streams ran 1.4-1.8x longer, r5.)
-    SH_HIP(hipStreamCreateWithFlags(&c->stB, hipStreamNonBlocking));
-    SH_HIP(hipStreamCreateWithFlags(&c->stC, hipStreamNonBlocking));
-    SH_HIP(hipStreamCreateWithFlags(&c->stD, hipStreamNonBlocking));
-    SH_HIP(hipStreamCreateWithFlags(&c->stE, hipStreamNonBlocking));
-    SH_HIP(hipStreamCreateWithFlags(&c->stF, hipStreamNonBlocking));
-    for (auto& e : c->ev) SH_HIP(hipEventCreate(&e));
-    for (auto& e : c->evSleep) SH_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventBlockingSync));
-    for (auto& e : c->ringEv) SH_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (Stream* s : {&c->st, &c->stB, &c->stC, &c->stD, &c->stE, &c->stF}) *s = Stream(hipStreamNonBlocking);
+    for (auto& e : c->ev) e = Event(hipEventDefault);
+    for (auto& e : c->evSleep) e = Event(hipEventDisableTiming | hipEventBlockingSync);
+    for (auto& e : c->ringEv) e = Event(hipEventDisableTiming);
     // the streamed upload's pinned ring, pinned while the caller builds or
     // loads the index (pinning 256 MB takes ~50 ms)
     Ctx* raw = c.get();
     raw->ringInit = std::thread([raw] {
         raw->place.bind();  // pinned pages first touched on the device's node
         (void)hipSetDevice(raw->device);
-        if (hipHostMalloc(reinterpret_cast<void**>(&raw->ring), Ctx::kRingSlots * Ctx::kRingSlot, hipHostMallocPortable) !=
-            hipSuccess) {
-            raw->ring = nullptr;
+        try {
+            raw->ring.reserve(Ctx::kRingSlots * Ctx::kRingSlot, hipHostMallocPortable);
+        } catch (const Error&) {
             raw->ringFailed = true;
         }
-        if (hipHostMalloc(reinterpret_cast<void**>(&raw->downRing), Ctx::kDownSlots * Ctx::kDownSlot,
-                          hipHostMallocPortable) != hipSuccess)
-            raw->downRing = nullptr;  // no compact download: hits go to a pinned sink whole
+        try {
+            raw->downRing.reserve(Ctx::kDownSlots * Ctx::kDownSlot / sizeof(uint64_t), hipHostMallocPortable);
+        } catch (const Error&) {  // no compact download: hits go to a pinned sink whole
+        }
     });
     for (auto& sl : c->slot) {
-        for (hipEvent_t* e : {&sl.fmStart, &sl.seedDone, &sl.seedDone0, &sl.seedMid, &sl.fmBegin, &sl.fmDone,
-                              &sl.textStart, &sl.textDone, &sl.free, &sl.textMid0, &sl.textMid1})
-            SH_HIP(hipEventCreate(e));
+        for (Event* e : {&sl.fmStart, &sl.seedDone, &sl.seedDone0, &sl.seedMid, &sl.fmBegin, &sl.fmDone, &sl.textStart,
+                         &sl.textDone, &sl.free, &sl.textMid0, &sl.textMid1})
+            *e = Event(hipEventDefault);
         sl.small.reserve(8);
         sl.queues.reserve(768);
     }
-    for (void*& p : c->outStage) SH_HIP(hipHostMalloc(&p, Ctx::kOutChunk));
+    for (auto& p : c->outStage) p.reserve(Ctx::kOutChunk);
     c->small.reserve(8);
     c->counters.reserve(kCounters);
     SH_HIP(hipMemset(c->counters.ptr, 0, kCounters * sizeof(unsigned long long)));
@@ -257,6 +253,14 @@ Ctx* openImage(int device, const uint8_t* buf, size_t bytes) {
         for (uint32_t p = 0; p < parts.size(); ++p) buildKmerTable(partOf(c.get(), p), K, c->st);
     }
     return c.release();
+}
+
+// SAHARA_TIMING=2: a call's host-side marks (Ctx::mark), from t0 on, printed (stderr) at its end
+static void traceBegin(Ctx* c, std::chrono::steady_clock::time_point t0) {
+    const char* te = std::getenv("SAHARA_TIMING");
+    c->traceOn = te && std::atoi(te) >= 2;
+    c->traceT0 = t0;
+    c->trace.clear();
 }
 
 }  // namespace sahara
@@ -432,12 +436,7 @@ int sahara_gpu_stage(void* ctx, const uint8_t* ranks, uint64_t n_patterns, uint3
 int sahara_gpu_run(void* ctx, int count, uint64_t* n_hits) {
     return guarded([&] {
         Ctx* c = ctxOf(ctx);
-        const char* te = std::getenv("SAHARA_TIMING");  // 2: host-side marks of the call (stderr)
-        c->traceOn = te && std::atoi(te) >= 2;
-        if (c->traceOn) {
-            c->trace.clear();
-            c->traceT0 = std::chrono::steady_clock::now();
-        }
+        traceBegin(c, std::chrono::steady_clock::now());
         run(c, count != 0);
         if (n_hits) *n_hits = c->nout;
         if (c->traceOn) {
@@ -615,19 +614,17 @@ static void copyOut(Ctx* c, void* dst, const void* src, size_t bytes) {
         SH_HIP(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
         return;
     }
-    for (void*& p : c->outStage)
-        if (!p) SH_HIP(hipHostMalloc(&p, Ctx::kOutChunk));
     const size_t n = (bytes + Ctx::kOutChunk - 1) / Ctx::kOutChunk;
     auto len = [&](size_t k) { return std::min(Ctx::kOutChunk, bytes - k * Ctx::kOutChunk); };
     for (size_t k = 0; k <= n; ++k) {
         if (k < n) {
-            SH_HIP(hipMemcpyAsync(c->outStage[k & 1], static_cast<const char*>(src) + k * Ctx::kOutChunk, len(k),
+            SH_HIP(hipMemcpyAsync(c->outStage[k & 1].ptr, static_cast<const char*>(src) + k * Ctx::kOutChunk, len(k),
                                   hipMemcpyDeviceToHost, c->st));
             SH_HIP(hipEventRecord(c->ev[k & 1], c->st));
         }
         if (k > 0) {
             SH_HIP(hipEventSynchronize(c->ev[(k - 1) & 1]));
-            parallelCopy(static_cast<char*>(dst) + (k - 1) * Ctx::kOutChunk, c->outStage[(k - 1) & 1], len(k - 1));
+            parallelCopy(static_cast<char*>(dst) + (k - 1) * Ctx::kOutChunk, c->outStage[(k - 1) & 1].ptr, len(k - 1));
         }
     }
 }
@@ -636,8 +633,8 @@ static void copyOut(Ctx* c, void* dst, const void* src, size_t bytes) {
 // issued batches may still run and copy into the sink).
 static void drainAll(Ctx* c) {
     drainPacking(c);  // chunks packed ahead: nothing reads the caller's buffer after the call
-    for (hipStream_t s : {c->st, c->stB, c->stC, c->stD, c->stE, c->stF})
-        if (s) (void)hipStreamSynchronize(s);
+    for (const Stream* s : {&c->st, &c->stB, &c->stC, &c->stD, &c->stE, &c->stF})
+        if (s->s) (void)hipStreamSynchronize(*s);
 }
 
 // SAHARA_TIMING=2: each chunk DMA's duration and rate from its events
@@ -652,6 +649,53 @@ static void printDmaTimes(Ctx* c) {
     c->dmaUsed = 0;
 }
 
+// ... of a streamed call, with its DMA times
+static void traceEnd(Ctx* c) {
+    std::sort(c->trace.begin(), c->trace.end());
+    for (auto& m : c->trace) std::fprintf(stderr, "[sahara]   %8.2f %s\n", m.first, m.second.c_str());
+    printDmaTimes(c);
+    c->traceOn = false;
+}
+
+// The query list of a reads call: n_reads reads, interleaved with their
+// reverse complements (reverse) and cut to `limit` patterns (--limit_queries
+// cuts the interleaved list, search.cpp:125-127); rows: the reads it takes.
+struct ReadRows {
+    uint64_t npat, rows;
+};
+static ReadRows readRows(int reverse, uint64_t n_reads, uint64_t limit) {
+    uint64_t npat = reverse ? 2 * n_reads : n_reads;
+    if (limit && limit < npat) npat = limit;
+    if (npat == 0) throw Error("no patterns");
+    return {npat, reverse ? (npat + 1) / 2 : npat};
+}
+
+// Hits (or records) a call's sink is sized for: what the last call found and
+// an eighth more (the bench's steady state), else 2 per pattern
+static uint64_t sinkEstimate(const Ctx* c, uint64_t npat) {
+    return c && c->lastHits ? c->lastHits + c->lastHits / 8 + 1024 : 2 * npat + 1024;
+}
+
+// a host buffer on its way to the caller, freed by freeHits (allocHits, allocPinned) or std::free
+using HostBuf = std::unique_ptr<void, void (*)(void*)>;
+
+// A streamed call fails after staging (the guard of searchStreamed and
+// searchReadsCompact): when this returns nothing of the call runs, reads the
+// caller's queries or writes into its sink, which the caller's owner frees
+// next (it is declared before the guard), and nothing stays staged.
+// packingOnly: no pass was started, only chunks may be packing ahead.
+static void abandonCall(Ctx* c, bool packingOnly) {
+    if (packingOnly) drainPacking(c);
+    else drainAll(c);
+    if (c->sk.compact) {
+        try {
+            c->expander->drain();
+        } catch (...) {
+        }
+    }
+    c->sk = {};
+}
+
 // sahara_gpu_search / sahara_gpu_search_reads: streamed upload, the pipelined
 // pass, the hits streamed into a pinned host sink batch by batch, then handed
 // to the caller (search.cpp:218-250 from host queries to host hits).
@@ -661,139 +705,94 @@ static void searchStreamed(Ctx* c, const uint8_t* src, uint64_t rows, bool rc, u
                            const PackedReads* packed = nullptr) {
     using clk = std::chrono::steady_clock;
     const auto tA = clk::now();
-    {
-        const char* te = std::getenv("SAHARA_TIMING");
-        c->traceOn = te && std::atoi(te) >= 2;
-        c->traceT0 = tA;
-        c->trace.clear();
-    }
+    traceBegin(c, tA);
+    HostBuf sink(nullptr, freeHits);
     stageStreamed(c, src, rows, rc, npat, len, pi, l, u, n_searches, edit, packed);
+    ScopeExit failed([c] { abandonCall(c, false); });
     const auto tB = clk::now();
-    c->sink = nullptr;
-    c->sinkCap = 0;
-    c->compactSink = c->sinkPinned = false;
     // --max_hits: per batch on the device (limitBatch), so the limited hits
     // stream to the host like any others; a multi-part index limits after
     // its parts merge, on the host (limitHits)
     const bool hostLimit = max_hits && !c->more.empty();
-    c->limitN = hostLimit ? 0u : max_hits;
-    if (!hostLimit) {  // sized from the last call (the bench's steady state), else 2 hits per pattern
+    c->sk.limitN = hostLimit ? 0u : max_hits;
+    if (!hostLimit) {
         // a first call takes a pooled buffer if there is one, but pins none:
         // pinning ~1 GB costs ~200 ms, ten times the pageable copy-out
-        const uint64_t est = c->lastHits ? c->lastHits + c->lastHits / 8 + 1024 : 2 * npat + 1024;
         bool pinned = false;
-        void* p = allocHits(est, &pinned, &c->sinkCap, c->lastHits != 0);
+        HostBuf p(allocHits(sinkEstimate(c, npat), &pinned, &c->sk.cap, c->lastHits != 0), freeHits);
         // hits go whole into a pinned sink (DMA; no host CPU or memory traffic
         // beyond the write), or, into pageable memory, as 8-B records that
         // host threads expand (Expander): a third of the PCIe bytes, but the
         // expansion reads and writes host memory the packing also needs
         // (at C3 it took ~4 ms per batch beside the packing, 300M against
         // 330M reads/s). SAHARA_COMPACT_DOWNLOAD=1 / SAHARA_FULL_DOWNLOAD=1 force one.
-        const bool compactOk = c->downRing && c->maxErr < 16 && c->I.n < (1ull << 32);
+        const bool compactOk = c->downRing.ptr && c->maxErr < 16 && c->I.n < (1ull << 32);
         const char* fe = std::getenv("SAHARA_FULL_DOWNLOAD");
         const char* ce = std::getenv("SAHARA_COMPACT_DOWNLOAD");
         const bool compact = compactOk && !(fe && std::atoi(fe)) && (!pinned || (ce && std::atoi(ce)));
         if (p && (pinned || compact)) {
-            c->sink = static_cast<sahara_hit*>(p);
-            c->sinkPinned = pinned;
-            c->compactSink = compact;
+            sink = std::move(p);
+            c->sk.sink = static_cast<sahara_hit*>(sink.get());
+            c->sk.pinned = pinned;
+            c->sk.compact = compact;
         } else {
-            freeHits(p);
-            c->sinkCap = 0;
+            c->sk.cap = 0;
         }
-        if (c->compactSink) {
+        if (c->sk.compact) {
             if (!c->expander)
                 c->expander = std::make_unique<Expander>(c->device, hostThreads(c, 8) - 1, &c->place);
             c->expander->setStarts(&c->I.recStarts);
             c->expander->mark = [c](const char* w, uint64_t i) { c->mark(w, i); };
             c->expander->reset();
-            c->downJobs = 0;
         }
     }
     const auto tC = clk::now();
-    try {
-        run(c, false);
-        c->limitN = 0;
-        uint32_t bad = 0;
-        SH_HIP(hipMemcpy(&bad, c->badFlag.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost));
-        if (bad) throw Error("pattern rank out of range for this index");
-    } catch (...) {
-        c->limitN = 0;
-        drainAll(c);
-        if (c->compactSink) {
-            try {
-                c->expander->drain();  // nothing may write into the sink once it is freed
-            } catch (...) {
-            }
-        }
-        freeHits(c->sink);
-        c->sink = nullptr;
-        c->staged = c->streaming = false;
-        throw;
-    }
-    if (c->compactSink) {
-        try {
-            c->expander->drain();
-        } catch (...) {
-            freeHits(c->sink);
-            c->sink = nullptr;
-            throw;
-        }
-    }
+    run(c, false);
+    c->sk.limitN = 0;
+    uint32_t bad = 0;
+    SH_HIP(hipMemcpy(&bad, c->badFlag.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (bad) throw Error("pattern rank out of range for this index");
+    failed.dismiss();
+    c->sk.sink = nullptr;  // the pass is over; `sink` frees it should the expansion or the output fail
+    if (c->sk.compact) c->expander->drain();
     c->mark("run end", 0);
-    c->streaming = false;  // every chunk is up: sahara_gpu_run may re-run the staged patterns
+    c->sk.streaming = false;  // every chunk is up: sahara_gpu_run may re-run the staged patterns
     c->stats.stage_ms = c->up.hostMs;
     for (int b = 0; b < 3; ++b) c->stats.upload_chunks[b] = c->up.chunks[b];
     const auto t0 = std::chrono::steady_clock::now();
-    sahara_hit* buf = c->sink;
-    c->sink = nullptr;
-    try {
-        if (hostLimit) {
-            std::vector<sahara_hit> v(c->nout);
-            if (c->nout) SH_HIP(hipMemcpy(v.data(), c->out.ptr, c->nout * sizeof(sahara_hit), hipMemcpyDeviceToHost));
-            limitHits(v, max_hits);
-            handOver(v, hits, n_hits);
-        } else {
-            if (buf && c->nout > c->sinkCap) {  // more hits than the sink holds: a bigger buffer, copied whole
-                freeHits(buf);
-                buf = nullptr;
-                c->sinkDone = 0;
-            }
-            bool pinned = buf != nullptr && c->sinkPinned;
-            if (!buf) {
-                c->sinkDone = 0;
-                buf = static_cast<sahara_hit*>(allocHits(c->nout, &pinned, nullptr, c->lastHits != 0));
-                if (!buf) throw Error("out of host memory for hits");
-            }
-            if (c->nout > c->sinkDone) {  // the rest (or all) of the hits
-                const size_t bytes = (c->nout - c->sinkDone) * sizeof(sahara_hit);
-                if (pinned) {
-                    SH_HIP(hipMemcpyAsync(buf + c->sinkDone, c->out.ptr + c->sinkDone, bytes, hipMemcpyDeviceToHost,
-                                          c->st));
-                    SH_HIP(hipStreamSynchronize(c->st));
-                } else {
-                    copyOut(c, buf + c->sinkDone, c->out.ptr + c->sinkDone, bytes);
-                }
-            }
-            *hits = buf;
-            *n_hits = c->nout;
-            buf = nullptr;
+    if (hostLimit) {
+        std::vector<sahara_hit> v(c->nout);
+        if (c->nout) SH_HIP(hipMemcpy(v.data(), c->out.ptr, c->nout * sizeof(sahara_hit), hipMemcpyDeviceToHost));
+        limitHits(v, max_hits);
+        handOver(v, hits, n_hits);
+    } else {
+        if (sink && c->nout > c->sk.cap) sink.reset();  // more hits than the sink holds: a bigger buffer, copied whole
+        bool pinned = sink != nullptr && c->sk.pinned;
+        if (!sink) {
+            c->sk.done = 0;
+            sink.reset(allocHits(c->nout, &pinned, nullptr, c->lastHits != 0));
+            if (!sink) throw Error("out of host memory for hits");
         }
-    } catch (...) {
-        freeHits(buf);
-        throw;
+        sahara_hit* buf = static_cast<sahara_hit*>(sink.get());
+        if (c->nout > c->sk.done) {  // the rest (or all) of the hits
+            const size_t bytes = (c->nout - c->sk.done) * sizeof(sahara_hit);
+            if (pinned) {
+                SH_HIP(hipMemcpyAsync(buf + c->sk.done, c->out.ptr + c->sk.done, bytes, hipMemcpyDeviceToHost, c->st));
+                SH_HIP(hipStreamSynchronize(c->st));
+            } else {
+                copyOut(c, buf + c->sk.done, c->out.ptr + c->sk.done, bytes);
+            }
+        }
+        *hits = static_cast<sahara_hit*>(sink.release());
+        *n_hits = c->nout;
     }
-    freeHits(buf);  // the sink of a max_hits call
     c->lastHits = c->nout;
     c->stats.output_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (std::getenv("SAHARA_TIMING")) {  // where a call's wall time goes (stderr)
         auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
         std::fprintf(stderr, "[sahara] stage %.1f ms, sink %.1f ms, pass %.1f ms (host packing %.1f ms), output %.1f ms\n",
                      ms(tA, tB), ms(tB, tC), ms(tC, t0), c->up.hostMs, c->stats.output_ms);
-        std::sort(c->trace.begin(), c->trace.end());
-        for (auto& m : c->trace) std::fprintf(stderr, "[sahara]   %8.2f %s\n", m.first, m.second.c_str());
-        printDmaTimes(c);
-        c->traceOn = false;
+        traceEnd(c);
     }
 }
 
@@ -812,11 +811,8 @@ int sahara_gpu_search_reads(void* ctx, const uint8_t* reads, uint64_t n_reads, u
     return guarded([&] {
         Ctx* c = ctxOf(ctx);
         if (c->I.sigma != 5 && c->I.sigma != 6) throw Error("reverse complements need a dna4 or dna5 index");
-        uint64_t npat = reverse ? 2 * n_reads : n_reads;
-        if (limit && limit < npat) npat = limit;  // --limit_queries cuts the interleaved list (search.cpp:125-127)
-        if (npat == 0) throw Error("no patterns");
-        const uint64_t rows = reverse ? (npat + 1) / 2 : npat;
-        searchStreamed(c, reads, rows, reverse != 0, npat, len, pi, l, u, n_searches, edit, max_hits, hits, n_hits);
+        const ReadRows R = readRows(reverse, n_reads, limit);
+        searchStreamed(c, reads, R.rows, reverse != 0, R.npat, len, pi, l, u, n_searches, edit, max_hits, hits, n_hits);
     });
 }
 
@@ -831,105 +827,74 @@ static void searchReadsCompact(Ctx* c, const uint8_t* reads, uint64_t n_reads, u
     const auto tA = clk::now();
     if (c->I.sigma != 5 && c->I.sigma != 6) throw Error("reverse complements need a dna4 or dna5 index");
     if (!c->more.empty()) throw Error("compact hit records need a single-part index (text < 2^32 symbols)");
-    uint64_t npat = reverse ? 2 * n_reads : n_reads;
-    if (limit && limit < npat) npat = limit;  // --limit_queries (search.cpp:125-127)
-    if (npat == 0) throw Error("no patterns");
-    const uint64_t rows = reverse ? (npat + 1) / 2 : npat;
-    {
-        const char* te = std::getenv("SAHARA_TIMING");
-        c->traceOn = te && std::atoi(te) >= 2;
-        c->traceT0 = tA;
-        c->trace.clear();
-    }
+    const ReadRows R = readRows(reverse, n_reads, limit);
+    traceBegin(c, tA);
     for (uint64_t i = 0; i < (uint64_t)n_searches * len; ++i)  // before staging: a refused call stages nothing
         if (u[i] > 15) throw Error("compact hit records hold at most 15 errors");
-    stageStreamed(c, reads, rows, reverse != 0, npat, len, pi, l, u, n_searches, edit, packed);
-    c->sink = nullptr;
-    c->compactSink = c->sinkPinned = false;
+    HostBuf recs(nullptr, freeHits);
+    stageStreamed(c, reads, R.rows, reverse != 0, R.npat, len, pi, l, u, n_searches, edit, packed);
+    // (until the pass starts only the packing can be reading the caller's reads)
+    bool passStarted = false;
+    ScopeExit failed([&] { abandonCall(c, !passStarted); });
     // the sink, sized from the last call (else 2 hits per pattern), always
     // page-locked: the device writes into it
-    const uint64_t est = c->lastHits ? c->lastHits + c->lastHits / 8 + 1024 : 2 * npat + 1024;
     bool pinned = false;
     size_t capBytes = 0;
-    void* sinkMem = nullptr;
-    try {
-        sinkMem = allocPinned(est * 8, &pinned, &capBytes, true, true);
-        if (!sinkMem) throw Error("out of host memory for hits");
-        c->blockRecs = pinned ? static_cast<uint64_t*>(sinkMem) : nullptr;
-        c->sinkCap = pinned ? capBytes / 8 : 0;
-        if (c->sinkCap) c->outRecs.reserve(c->sinkCap);
-    } catch (...) {  // nothing may stream from the caller's reads after the call
-        drainPacking(c);
-        freeHits(sinkMem);
-        c->blockRecs = nullptr;
-        c->staged = c->streaming = false;
-        throw;
-    }
-    auto* recs = static_cast<uint64_t*>(sinkMem);
+    recs.reset(allocPinned(sinkEstimate(c, R.npat) * 8, &pinned, &capBytes, true, true));
+    if (!recs) throw Error("out of host memory for hits");
+    c->sk.blockRecs = pinned ? static_cast<uint64_t*>(recs.get()) : nullptr;
+    c->sk.cap = pinned ? capBytes / 8 : 0;
+    if (c->sk.cap) c->outRecs.reserve(c->sk.cap);
     uint64_t recCap = capBytes / 8;
-    try {
-        run(c, false);
-        uint32_t bad = 0;
-        SH_HIP(hipMemcpy(&bad, c->badFlag.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost));
-        if (bad) throw Error("pattern rank out of range for this index");
-        const auto t0 = clk::now();
-        if (!c->blockRecs || c->sinkDone < c->nout) {
-            // the sink held too few (or is not pinned): the records of every
-            // batch again, from the device-resident hits, into one that fits
-            if (c->nout > recCap) {
-                freeHits(recs);
-                recs = nullptr;
-                recs = static_cast<uint64_t*>(allocPinned(c->nout * 8, &pinned, &capBytes, true, true));
-                if (!recs) throw Error("out of host memory for hits");
-                recCap = capBytes / 8;
-            }
-            uint64_t* dst = recs;
-            if (!pinned) {
-                c->outC.reserve(std::max<uint64_t>(c->nout, 1));
-                dst = c->outC.ptr;
-            }
-            uint64_t b0 = 0;
-            for (size_t b = 0; b < c->batchQ0.size(); ++b) {
-                launchCompactHits(c->out.ptr + b0, c->batchEnd[b] - b0, c->batchQ0[b], c->I.dRecStarts.ptr, dst + b0,
-                                  c->st, pinned ? 256u : 8192u);
-                b0 = c->batchEnd[b];
-            }
-            if (!pinned && c->nout) SH_HIP(hipMemcpyAsync(recs, dst, c->nout * 8, hipMemcpyDeviceToHost, c->st));
-            SH_HIP(hipStreamSynchronize(c->st));
+    passStarted = true;
+    run(c, false);
+    uint32_t bad = 0;
+    SH_HIP(hipMemcpy(&bad, c->badFlag.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (bad) throw Error("pattern rank out of range for this index");
+    const auto t0 = clk::now();
+    if (!c->sk.blockRecs || c->sk.done < c->nout) {
+        // the sink held too few (or is not pinned): the records of every
+        // batch again, from the device-resident hits, into one that fits
+        if (c->nout > recCap) {
+            recs.reset();
+            recs.reset(allocPinned(c->nout * 8, &pinned, &capBytes, true, true));
+            if (!recs) throw Error("out of host memory for hits");
+            recCap = capBytes / 8;
         }
-        c->stats.output_ms = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
-    } catch (...) {
-        drainAll(c);
-        c->blockRecs = nullptr;
-        freeHits(recs);
-        c->staged = c->streaming = false;
-        throw;
+        uint64_t* dst = static_cast<uint64_t*>(recs.get());
+        if (!pinned) {
+            c->outC.reserve(std::max<uint64_t>(c->nout, 1));
+            dst = c->outC.ptr;
+        }
+        uint64_t b0 = 0;
+        for (size_t b = 0; b < c->batchQ0.size(); ++b) {
+            launchCompactHits(c->out.ptr + b0, c->batchEnd[b] - b0, c->batchQ0[b], c->I.dRecStarts.ptr, dst + b0,
+                              c->st, pinned ? 256u : 8192u);
+            b0 = c->batchEnd[b];
+        }
+        if (!pinned && c->nout) SH_HIP(hipMemcpyAsync(recs.get(), dst, c->nout * 8, hipMemcpyDeviceToHost, c->st));
+        SH_HIP(hipStreamSynchronize(c->st));
     }
-    c->blockRecs = nullptr;
-    c->streaming = false;
+    c->stats.output_ms = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+    failed.dismiss();
+    c->sk.blockRecs = nullptr;
+    c->sk.streaming = false;
     c->stats.stage_ms = c->up.hostMs;
     for (int b = 0; b < 3; ++b) c->stats.upload_chunks[b] = c->up.chunks[b];
     const size_t nb = c->batchQ0.size();
-    auto* q0 = static_cast<uint64_t*>(std::malloc(std::max<size_t>(nb, 1) * 8));
-    auto* end = static_cast<uint64_t*>(std::malloc(std::max<size_t>(nb, 1) * 8));
-    if (!q0 || !end) {
-        std::free(q0);
-        std::free(end);
-        freeHits(recs);
-        throw Error("out of host memory for hit blocks");
-    }
-    for (size_t b = 0; b < nb; ++b) {
-        q0[b] = c->batchQ0[b];
-        end[b] = c->batchEnd[b];
-    }
+    HostBuf q0(std::malloc(std::max<size_t>(nb, 1) * 8), std::free);
+    HostBuf end(std::malloc(std::max<size_t>(nb, 1) * 8), std::free);
+    if (!q0 || !end) throw Error("out of host memory for hit blocks");
+    if (nb) std::memcpy(q0.get(), c->batchQ0.data(), nb * 8);
+    if (nb) std::memcpy(end.get(), c->batchEnd.data(), nb * 8);
     if (c->recStartsEnd.size() != c->I.recStarts.size() + 1) {
         c->recStartsEnd = c->I.recStarts;
         c->recStartsEnd.push_back(c->I.n);
     }
-    out->recs = recs;
+    out->recs = static_cast<uint64_t*>(recs.release());
     out->n_hits = c->nout;
-    out->block_qid0 = q0;
-    out->block_end = end;
+    out->block_qid0 = static_cast<uint64_t*>(q0.release());
+    out->block_end = static_cast<uint64_t*>(end.release());
     out->n_blocks = nb;
     out->rec_starts = c->recStartsEnd.data();
     out->n_records = c->I.recStarts.size();
@@ -938,10 +903,7 @@ static void searchReadsCompact(Ctx* c, const uint8_t* reads, uint64_t n_reads, u
         auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
         std::fprintf(stderr, "[sahara] compact call %.1f ms (host packing %.1f ms), output %.1f ms\n", ms(tA, clk::now()),
                      c->up.hostMs, c->stats.output_ms);
-        std::sort(c->trace.begin(), c->trace.end());
-        for (auto& m : c->trace) std::fprintf(stderr, "[sahara]   %8.2f %s\n", m.first, m.second.c_str());
-        printDmaTimes(c);
-        c->traceOn = false;
+        traceEnd(c);
     }
 }
 
@@ -962,12 +924,9 @@ int sahara_gpu_search_packed(void* ctx, const uint8_t* codes, uint64_t sym0, con
     return guarded([&] {
         Ctx* c = ctxOf(ctx);
         if (!codes || (n_count && !n_pos)) throw Error("sahara_gpu_search_packed: null input");
-        uint64_t npat = reverse ? 2 * n_reads : n_reads;
-        if (limit && limit < npat) npat = limit;  // --limit_queries cuts the interleaved list (search.cpp:125-127)
-        if (npat == 0) throw Error("no patterns");
-        const uint64_t rows = reverse ? (npat + 1) / 2 : npat;
+        const ReadRows R = readRows(reverse, n_reads, limit);
         const PackedReads pk{sym0, n_pos, n_count};
-        searchStreamed(c, codes, rows, reverse != 0, npat, len, pi, l, u, n_searches, edit, max_hits, hits, n_hits,
+        searchStreamed(c, codes, R.rows, reverse != 0, R.npat, len, pi, l, u, n_searches, edit, max_hits, hits, n_hits,
                        &pk);
     });
 }
@@ -992,7 +951,7 @@ int sahara_gpu_prepare(void* ctx, uint64_t n_patterns, uint32_t len) {
         if (c) SH_HIP(hipSetDevice(c->device));
         // the sink the first compact call asks the pool for (searchReadsCompact),
         // pinned now and handed back to the pool, where the call finds it
-        const uint64_t est = c && c->lastHits ? c->lastHits + c->lastHits / 8 + 1024 : 2 * n_patterns + 1024;
+        const uint64_t est = sinkEstimate(c, n_patterns);
         bool pinned = false;
         size_t capBytes = 0;
         {
@@ -1075,14 +1034,11 @@ int sahara_gpu_search_best(void* ctx, const uint8_t* ranks, uint64_t n_patterns,
             stage(c, src, todo.size(), len, pi + off, l + off, u + off, n_searches[j], 1);
             // --max_hits per batch on the device (single part; the host pass
             // below is then a no-op on what is left)
-            c->limitN = c->more.empty() ? max_hits : 0u;
-            try {
+            c->sk.limitN = c->more.empty() ? max_hits : 0u;
+            {
+                const ScopeExit limitOff([c] { c->sk.limitN = 0; });
                 run(c, false);
-            } catch (...) {
-                c->limitN = 0;
-                throw;
             }
-            c->limitN = 0;
             std::vector<sahara_hit> v(c->nout);
             if (c->nout) SH_HIP(hipMemcpy(v.data(), c->out.ptr, c->nout * sizeof(sahara_hit), hipMemcpyDeviceToHost));
             acc.search_ms += c->stats.search_ms;

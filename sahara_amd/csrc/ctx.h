@@ -3,14 +3,11 @@
 // (pass.cpp) share.
 #pragma once
 #include <hip/hip_runtime.h>
-#include <pthread.h>
-#include <sched.h>
 
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
 #include <cstdint>
-#include <deque>
 #include <functional>
 #include <memory>
 #include <mutex>
@@ -20,169 +17,12 @@
 
 #include "../../include/sahara_hip.h"
 #include "device_index.h"
+#include "host_pool.h"
 #include "search.h"
 
 namespace sahara {
 
 extern thread_local std::string g_err;  // sahara_gpu_last_error
-
-// NUMA placement of a context's own host threads that touch its pinned
-// buffers (the pass's finisher, the hit expander, the ring pinning): the CPUs
-// of the NUMA node the GPU hangs off (/sys/bus/pci/devices/<bdf>/numa_node),
-// as far as the process may use them. The packing pool reads the caller's
-// buffers, wherever those are, and stays unbound (staging.cpp hostPool).
-// node = -1 (unknown, or SAHARA_NUMA=0): threads stay where the OS puts them.
-struct Placement {
-    int node = -1;
-    int ncpus = 0;      // CPUs the context's threads are bound to (0: not bound)
-    cpu_set_t cpus;
-    Placement() { CPU_ZERO(&cpus); }
-    void bind() const {
-        if (ncpus > 0) (void)pthread_setaffinity_np(pthread_self(), sizeof(cpus), &cpus);
-    }
-};
-
-// Host worker threads of a context (pattern packing for the upload), started
-// once: a streamed upload packs several chunks per call, and fresh threads per
-// chunk measured slower than the link.
-class HostPool {
-public:
-    explicit HostPool(unsigned workers, const Placement* pl = nullptr) {
-        for (unsigned i = 1; i <= workers; ++i)
-            ts_.emplace_back([this, i, pl] {
-                if (pl) pl->bind();
-                loop(i);
-            });
-    }
-    ~HostPool() {
-        {
-            std::lock_guard<std::mutex> g(mu_);
-            stop_ = true;
-        }
-        cv_.notify_all();
-        for (auto& t : ts_) t.join();
-    }
-    unsigned size() const { return (unsigned)ts_.size() + 1; }
-    // f(t) for every t in [0, size()), t = 0 on the calling thread; f must not throw
-    void run(const std::function<void(unsigned)>& f) {
-        {
-            std::lock_guard<std::mutex> g(mu_);
-            job_ = &f;
-            pending_ = (unsigned)ts_.size();
-            ++gen_;
-        }
-        cv_.notify_all();
-        f(0);
-        std::unique_lock<std::mutex> lk(mu_);
-        done_.wait(lk, [&] { return pending_ == 0; });
-        job_ = nullptr;
-    }
-
-private:
-    void loop(unsigned id) {
-        uint64_t seen = 0;
-        for (;;) {
-            const std::function<void(unsigned)>* f;
-            {
-                std::unique_lock<std::mutex> lk(mu_);
-                cv_.wait(lk, [&] { return stop_ || gen_ != seen; });
-                if (stop_) return;
-                seen = gen_;
-                f = job_;
-            }
-            (*f)(id);
-            std::lock_guard<std::mutex> g(mu_);
-            if (--pending_ == 0) done_.notify_all();
-        }
-    }
-    std::vector<std::thread> ts_;
-    std::mutex mu_;
-    std::condition_variable cv_, done_;
-    const std::function<void(unsigned)>* job_ = nullptr;
-    uint64_t gen_ = 0;
-    unsigned pending_ = 0;
-    bool stop_ = false;
-};
-
-// Host threads that pack the streamed upload (staging.cpp): a FIFO of tasks
-// rather than fork-join rounds, so that the pieces of several chunks are in
-// flight at once. A fork-join round per chunk (13 pieces of 4M symbols on 16
-// threads at C3) left threads idle at every chunk's end and stopped packing
-// whenever the issuing thread was not inside it; queued chunks keep every
-// thread busy while the issuing thread enqueues kernels or waits for a slot.
-class TaskPool {
-public:
-    explicit TaskPool(unsigned workers, const Placement* pl = nullptr) {
-        for (unsigned i = 0; i < std::max(workers, 1u); ++i)
-            ts_.emplace_back([this, pl] {
-                if (pl) pl->bind();
-                loop();
-            });
-    }
-    ~TaskPool() {  // tasks still queued are dropped (callers wait for theirs first)
-        {
-            std::lock_guard<std::mutex> g(mu_);
-            stop_ = true;
-        }
-        cv_.notify_all();
-        for (auto& t : ts_) t.join();
-    }
-    unsigned size() const { return (unsigned)ts_.size(); }
-    void post(std::function<void()> f) {
-        {
-            std::lock_guard<std::mutex> g(mu_);
-            q_.push_back(std::move(f));
-        }
-        cv_.notify_one();
-    }
-    void postMany(std::vector<std::function<void()>>& fs) {
-        {
-            std::lock_guard<std::mutex> g(mu_);
-            for (auto& f : fs) q_.push_back(std::move(f));
-        }
-        cv_.notify_all();
-        fs.clear();
-    }
-
-private:
-    void loop() {
-        for (;;) {
-            std::function<void()> f;
-            {
-                std::unique_lock<std::mutex> lk(mu_);
-                cv_.wait(lk, [&] { return stop_ || !q_.empty(); });
-                if (stop_) return;
-                f = std::move(q_.front());
-                q_.pop_front();
-            }
-            f();
-        }
-    }
-    std::vector<std::thread> ts_;
-    std::mutex mu_;
-    std::condition_variable cv_;
-    std::deque<std::function<void()>> q_;
-    bool stop_ = false;
-};
-
-// A group of tasks posted to a TaskPool that the poster waits for.
-struct TaskGroup {
-    std::atomic<uint64_t> left{0};
-    std::mutex mu;
-    std::condition_variable cv;
-    void begin(uint64_t n) { left.store(n, std::memory_order_relaxed); }
-    void oneDone() {
-        if (left.fetch_sub(1, std::memory_order_acq_rel) == 1) {
-            std::lock_guard<std::mutex> g(mu);
-            cv.notify_all();
-        }
-    }
-    void wait() {
-        if (left.load(std::memory_order_acquire) == 0) return;
-        std::unique_lock<std::mutex> lk(mu);
-        cv.wait(lk, [&] { return left.load(std::memory_order_acquire) == 0; });
-    }
-};
 
 // Host side of sahara_gpu_search's compact hit download: batch by batch, the
 // 8-B records (search.hip kCompactHits) land in pinned staging memory on
@@ -311,10 +151,18 @@ private:
 // C5, C2 within noise (profiles/r05_text_steps_ab.txt).
 constexpr uint32_t kTextStepsDefault = 2;
 constexpr uint32_t kRefillAtDefault = 8;
+// Ownership and teardown. Every handle of a context has an owning type
+// (DevBuf, Stream, Event, PinnedBuf, unique_ptr), so ~Ctx releases nothing by
+// hand: it only ends the host threads, in the order pinning thread, expander,
+// packing pool, after which no thread can touch the context's memory. The
+// members then go in reverse order of declaration, in two groups: first the
+// streams, events and page-locked buffers (with the slots, whose events go
+// before their buffers), which therefore stand at the end of the struct; then
+// the device buffers and the index parts, which stand before them. A new
+// member goes with its kind.
 struct Ctx {
     int device = 0;
     Placement place;                      // NUMA node of the device; the context's threads run there
-    hipStream_t st = nullptr;
     int numCU = 0;
     DeviceIndex I;
     // A text of 2^32 - 2 symbols or more is indexed in parts (splitRecords):
@@ -337,53 +185,17 @@ struct Ctx {
     uint32_t nsearch = 0;
     uint32_t maxErr = 0;
     bool edit = true;
-    bool staged = false;
     bool verify = true;
     bool locateSA = true;
     uint32_t split = 1;                   // text-phase threshold (rows per interval)
     uint32_t textSteps = kTextStepsDefault;  // text-phase micro-steps per lane per wave iteration
     uint32_t refillAt = kRefillAtDefault;    // text-phase batch refill threshold (idle lanes)
 
-    // work buffers. Batches rotate over kSlots slots so that seeds and the FM
-    // phase run batches ahead (streams `stD`, `st`) of the text phase (stream
-    // `stB`), while earlier batches run their locate and sort (stream `stC`).
-    static constexpr int kSlots = 5;
-    struct Slot {
-        DevBuf<uint4> hits, tasks, seeds;  // seeds: starting cursors (kSeedItems -> kSearchFM)
-        DevBuf<uint32_t> seedItem;
-        DevBuf<uint32_t> qcnt, rank;      // rows ranked at emission: per-query row counts (zero between
-                                          // batches), per hit slot its first row's place in its segment
-        DevBuf<uint32_t> small;           // -, hitCount, flags, filled, taskCount, seed tasks, seedCount
-        DevBuf<uint32_t> queues;          // striped work counters: FM seeds [0, 256), text tasks: the seed
-                                          // tasks [256, 512), the FM phase's [512, 768)
-        // kernel spans, each recorded on the kernel's own stream right around
-        // its launch(es): seeds fmStart..seedDone (sD), FM fmBegin..fmDone
-        // (sA), text textStart..textDone (sB); seedDone0: the batch's first
-        // seed tasks are written
-        hipEvent_t fmStart = nullptr, seedDone = nullptr, seedDone0 = nullptr, seedMid = nullptr, fmBegin = nullptr,
-                   fmDone = nullptr, textStart = nullptr, textDone = nullptr, free = nullptr;
-        // the first batch of an early pass launches its text phase twice:
-        // textStart..textMid0, then textMid1..textDone (not the wait between)
-        hipEvent_t textMid0 = nullptr, textMid1 = nullptr;
-        bool twoText = false;
-        bool seedsInParts = false;        // seeds in parts: fmStart..seedDone0, then Ctx::partEv's pairs
-        uint32_t seedParts = 0;           // (the later parts: Ctx::partEv[2 i], [2 i + 1] around part i)
-    } slot[kSlots];
-    hipStream_t stB = nullptr, stC = nullptr, stD = nullptr;  // text, locate / sort, seeds
-    std::vector<hipEvent_t> partEv;  // around the first batch's later seed launches (created on demand)
-    uint32_t* pinned = nullptr;           // host copies of the slots' small counters (8 u32 per batch)
-    // two pinned staging chunks for handing hits to pageable host memory: the
-    // DMA of one chunk overlaps the host copy out of the other (copyOut)
-    static constexpr size_t kOutChunk = 32u << 20;
-    void* outStage[2] = {nullptr, nullptr};
-    size_t pinnedCap = 0;
     bool pipeline = true;
     DevBuf<uint4> stack;                  // FM spill stack (stream st only)
     DevBuf<uint8_t> rawPats;              // staged pattern bytes before packing
     DevBuf<uint8_t> nibPats;              // the same, two symbols per byte as uploaded (stageIn)
     bool nibbleUpload = true;             // SAHARA_NIBBLE_UPLOAD=0: pattern bytes go up as given
-    uint8_t* nibHost = nullptr;           // pinned: the packed patterns on their way up (stage)
-    size_t nibHostCap = 0;
     DevBuf<uint32_t> small;               // scratch counters for single-stream helpers
     DevBuf<unsigned long long> counters;  // nodes, rank nodes, lines, lf steps, digest, text nodes, tasks
     DevBuf<uint64_t> qoff, k0, k1;        // per-query row segments of a batch; locate keys
@@ -395,11 +207,6 @@ struct Ctx {
     double stageMs = 0;                   // wall time of the last stage(): H2D, pack, validation
     uint32_t hitCap = 0, taskCap = 0;
     sahara_stats stats{};
-    hipEvent_t ev[8] = {};
-    // the finisher's waits in a streamed call (text done, row total, batch
-    // checked): blocking-sync events, so that it sleeps instead of spinning a
-    // CPU that the packing threads need (a 16-CPU quota on the GPU box)
-    hipEvent_t evSleep[3] = {};
 
     // Streamed query upload (sahara_gpu_search, sahara_gpu_search_reads): the
     // source rows go up in chunks, each packed on the host (two symbols per
@@ -436,14 +243,7 @@ struct Ctx {
     // stream processed shard by shard is checked once, not once per shard
     const uint64_t* nPosChecked = nullptr;
     uint64_t nCountChecked = 0;
-    bool streaming = false;
-    hipStream_t stE = nullptr, stF = nullptr;  // pattern upload; hit download (sink)
-    // SAHARA_TIMING=2: timing events around each chunk's DMA (bytes, events)
-    std::vector<std::pair<uint64_t, std::pair<hipEvent_t, hipEvent_t>>> dmaEv;
-    size_t dmaUsed = 0;
     static constexpr size_t kRingSlots = 8, kRingSlot = 32u << 20;  // 256 MB pinned
-    uint8_t* ring = nullptr;
-    hipEvent_t ringEv[kRingSlots] = {};
     // Chunks packed ahead (2-bit upload): chunk j packs into ring slot
     // j % kRingSlots on the pool's threads while the issuing thread still
     // enqueues earlier batches; uploadChunk waits for its pieces, then lists
@@ -460,42 +260,48 @@ struct Ctx {
     bool ringFailed = false;
     DevBuf<uint32_t> badFlag;             // device rank check of streamed chunks
     DevBuf<uint8_t> readRaw;              // streamed reads before the reverse-complement interleave
-    std::unique_ptr<TaskPool> pool;       // declared after packJobs: its threads end first
+    std::unique_ptr<TaskPool> pool;       // the packing threads (hostPool)
     unsigned poolCap = 0;
     Placement packPlace;                  // the pool's CPUs when bound
     int poolNode = -2;                    // NUMA node the pool is bound to (-1: unbound)
-    // host sink of sahara_gpu_search: each batch's sorted hits go to host
-    // memory (pinned) on stF while later batches search
-    sahara_hit* sink = nullptr;
-    uint64_t sinkCap = 0, sinkDone = 0;
-    bool sinkOk = false;
+    // The state of one call: staging starts it from Sink{} (stage,
+    // stageStreamed), the entry point fills in where its hits go, and a call
+    // that fails leaves it cleared (capi.cpp abandonCall).
+    struct Sink {
+        bool staged = false;              // patterns are staged: sahara_gpu_run may search them
+        bool streaming = false;           // ... chunk by chunk during the pass (Upload)
+        // host sink of sahara_gpu_search: each batch's sorted hits go to host
+        // memory on stF while later batches search: whole into pinned memory
+        // (pinned), or as 8-B records that the Expander expands (compact)
+        sahara_hit* sink = nullptr;
+        uint64_t cap = 0, done = 0;       // hits (records) the sink holds; those on their way into it
+        bool ok = false;                  // every batch so far went into the sink
+        bool compact = false, pinned = false;
+        uint64_t downJobs = 0;            // batches handed to the expander this call
+        uint64_t* blockRecs = nullptr;    // sahara_gpu_search_reads_compact's sink (below)
+        // --max_hits n applied per batch on the device (single-part indexes;
+        // limitBatch), 0: off
+        uint32_t limitN = 0;
+    } sk;
     uint64_t lastHits = 0;                // hits of the previous sahara_gpu_search (sink size estimate)
     // compact download into the sink (Expander): device records of the
     // pass, their pinned host staging, one event per batch's download
     // (batch b's records land in slot b % kDownSlots of a pinned ring,
     // pinned with the upload ring; the slot is reused once batch b is expanded)
-    bool compactSink = false, sinkPinned = false;
     DevBuf<uint64_t> outC;
     static constexpr size_t kDownSlots = 3, kDownSlot = 64u << 20;  // 8M records per batch
-    uint64_t* downRing = nullptr;
-    uint64_t downJobs = 0;                // batches handed to the expander this call
-    std::vector<hipEvent_t> downEv;
     std::unique_ptr<Expander> expander;
     // sahara_gpu_search_reads_compact: each batch's hits as 8-B records,
-    // made by kCompactHits in HBM (outRecs, sinkCap entries) and copied by a
-    // copy engine on stF into this pinned host buffer (sinkCap records); per
+    // made by kCompactHits in HBM (outRecs, sk.cap entries) and copied by a
+    // copy engine on stF into the pinned host buffer sk.blockRecs (sk.cap records); per
     // batch its first qid and one past its last record (the blocks of
     // sahara_hit_blocks). (Written by the kernel straight into the sink over
     // PCIe, the records held CU slots beside the text phase: C3 592M against
     // 632M reads/s with the copy engine, profiles/r03_pcie_compact_dma.txt.)
-    uint64_t* blockRecs = nullptr;
     DevBuf<uint64_t> outRecs;
     std::vector<uint64_t> batchQ0, batchEnd;
     std::vector<uint64_t> recStartsEnd;   // record starts + the text length (sahara_hit_blocks.rec_starts)
-    // --max_hits n applied per batch on the device (single-part indexes;
-    // limitBatch), 0: off
-    uint32_t limitN = 0;
-    DevBuf<uint32_t> limitCnt;
+    DevBuf<uint32_t> limitCnt;            // limitBatch's buffers (sk.limitN)
     DevBuf<uint64_t> limitOff;
     DevBuf<sahara_hit> limitBuf;
     // SAHARA_TIMING=2: host-side marks of one call (ms since its start, what)
@@ -510,40 +316,75 @@ struct Ctx {
         trace.emplace_back(t, std::string(what) + " " + std::to_string(i));
     }
 
+    // work buffers. Batches rotate over kSlots slots so that seeds and the FM
+    // phase run batches ahead (streams `stD`, `st`) of the text phase (stream
+    // `stB`), while earlier batches run their locate and sort (stream `stC`).
+    static constexpr int kSlots = 5;
+    struct Slot {
+        DevBuf<uint4> hits, tasks, seeds;  // seeds: starting cursors (kSeedItems -> kSearchFM)
+        DevBuf<uint32_t> seedItem;
+        DevBuf<uint32_t> qcnt, rank;      // rows ranked at emission: per-query row counts (zero between
+                                          // batches), per hit slot its first row's place in its segment
+        DevBuf<uint32_t> small;           // -, hitCount, flags, filled, taskCount, seed tasks, seedCount
+        DevBuf<uint32_t> queues;          // striped work counters: FM seeds [0, 256), text tasks: the seed
+                                          // tasks [256, 512), the FM phase's [512, 768)
+        // kernel spans, each recorded on the kernel's own stream right around
+        // its launch(es): seeds fmStart..seedDone (sD), FM fmBegin..fmDone
+        // (sA), text textStart..textDone (sB); seedDone0: the batch's first
+        // seed tasks are written
+        Event fmStart, seedDone, seedDone0, seedMid, fmBegin, fmDone, textStart, textDone, free;
+        // the first batch of an early pass launches its text phase twice:
+        // textStart..textMid0, then textMid1..textDone (not the wait between)
+        Event textMid0, textMid1;
+        bool twoText = false;
+        bool seedsInParts = false;        // seeds in parts: fmStart..seedDone0, then Ctx::partEv's pairs
+        uint32_t seedParts = 0;           // (the later parts: Ctx::partEv[2 i], [2 i + 1] around part i)
+    } slot[kSlots];
+
+    // Streams, events and page-locked memory: declared last, released first
+    // (the rule at the top of Ctx).
+    Stream st, stB, stC, stD;  // FM phase and single-stream work; text, locate / sort, seeds
+    Stream stE, stF;           // pattern upload; hit download (sink)
+    Event ev[8];
+    // the finisher's waits in a streamed call (text done, row total, batch
+    // checked): blocking-sync events, so that it sleeps instead of spinning a
+    // CPU that the packing threads need (a 16-CPU quota on the GPU box)
+    Event evSleep[3];
+    std::vector<Event> partEv;  // around the first batch's later seed launches (created on demand)
+    Event ringEv[kRingSlots];
+    std::vector<Event> downEv;
+    // SAHARA_TIMING=2: timing events around each chunk's DMA (bytes, events)
+    std::vector<std::pair<uint64_t, std::pair<Event, Event>>> dmaEv;
+    size_t dmaUsed = 0;
+    PinnedBuf<uint32_t> pinned;           // host copies of the slots' small counters (16 u32 per batch)
+    // two pinned staging chunks for handing hits to pageable host memory: the
+    // DMA of one chunk overlaps the host copy out of the other (copyOut)
+    static constexpr size_t kOutChunk = 32u << 20;
+    PinnedBuf<char> outStage[2];
+    PinnedBuf<uint8_t> nibHost;           // the packed patterns on their way up (stage)
+    PinnedBuf<uint8_t> ring;              // the upload ring (pinned by ringInit)
+    PinnedBuf<uint64_t> downRing;         // the compact download's ring (pinned with it)
+
+    // Host threads end here, before any member goes: the pinning thread
+    // (it assigns ring and downRing), the expander (it reads downRing and
+    // waits on downEv), the packing pool (it writes into ring).
     ~Ctx() {
-        // the pinning thread assigns ring and downRing: it must be done before
-        // either is read (a context closed or failed right after newCtx)
         if (ringInit.joinable()) ringInit.join();
         expander.reset();
-        for (hipEvent_t e : downEv) (void)hipEventDestroy(e);
-        for (hipEvent_t e : partEv) (void)hipEventDestroy(e);
-        if (downRing) (void)hipHostFree(downRing);
-        for (auto& e : ev)
-            if (e) (void)hipEventDestroy(e);
-        for (auto& e : evSleep)
-            if (e) (void)hipEventDestroy(e);
-        for (auto& e : ringEv)
-            if (e) (void)hipEventDestroy(e);
-        if (ring) (void)hipHostFree(ring);
-        if (stE) (void)hipStreamDestroy(stE);
-        for (auto& d : dmaEv) {
-            (void)hipEventDestroy(d.second.first);
-            (void)hipEventDestroy(d.second.second);
-        }
-        if (stF) (void)hipStreamDestroy(stF);
-        for (auto& sl : slot)
-            for (hipEvent_t e : {sl.fmStart, sl.seedDone, sl.seedDone0, sl.seedMid, sl.fmBegin, sl.fmDone, sl.textStart,
-                                 sl.textDone, sl.free, sl.textMid0, sl.textMid1})
-                if (e) (void)hipEventDestroy(e);
-        if (pinned) (void)hipHostFree(pinned);
-        if (nibHost) (void)hipHostFree(nibHost);
-        for (void* p : outStage)
-            if (p) (void)hipHostFree(p);
-        if (stB) (void)hipStreamDestroy(stB);
-        if (stC) (void)hipStreamDestroy(stC);
-        if (stD) (void)hipStreamDestroy(stD);
-        if (st) (void)hipStreamDestroy(st);
+        pool.reset();
     }
+};
+
+// f() when the scope ends, on every way out unless dismissed
+template <typename F>
+struct ScopeExit {
+    explicit ScopeExit(F g) : f(std::move(g)) {}
+    ~ScopeExit() {
+        if (armed) f();
+    }
+    void dismiss() { armed = false; }
+    F f;
+    bool armed = true;
 };
 
 template <typename F>

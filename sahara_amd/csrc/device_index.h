@@ -8,6 +8,7 @@
 #include <mutex>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "fm_layout.h"
@@ -62,6 +63,15 @@ struct DevBuf {  // minimal owning device buffer that only ever grows
         ptr = nullptr;
         cap = 0;
     }
+    // a new allocation of n elements that keeps the first `used`, copied on
+    // `st`; returns with st synchronised and the old allocation freed
+    void growKeeping(size_t n, size_t used, hipStream_t st) {
+        DevBuf grown;
+        grown.reserve(n);
+        if (used) SH_HIP(hipMemcpyAsync(grown.ptr, ptr, used * sizeof(T), hipMemcpyDeviceToDevice, st));
+        SH_HIP(hipStreamSynchronize(st));
+        *this = std::move(grown);
+    }
     ~DevBuf() { release(); }
     DevBuf() = default;
     DevBuf(const DevBuf&) = delete;
@@ -77,6 +87,66 @@ struct DevBuf {  // minimal owning device buffer that only ever grows
             o.cap = 0;
             o.base = nullptr;
         }
+        return *this;
+    }
+};
+
+// Owners of the other HIP handles: move-only, empty when default-constructed,
+// released on destruction (an error there is ignored). Stream and Event stand
+// wherever HIP takes the raw handle.
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    explicit Stream(unsigned flags) { SH_HIP(hipStreamCreateWithFlags(&s, flags)); }
+    Stream(Stream&& o) noexcept : s(o.s) { o.s = nullptr; }
+    Stream& operator=(Stream&& o) noexcept {
+        std::swap(s, o.s);  // (o releases what this held)
+        return *this;
+    }
+    ~Stream() {
+        if (s) (void)hipStreamDestroy(s);
+    }
+    operator hipStream_t() const { return s; }
+};
+
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    explicit Event(unsigned flags) { SH_HIP(hipEventCreateWithFlags(&e, flags)); }  // hipEventDefault: timing
+    Event(Event&& o) noexcept : e(o.e) { o.e = nullptr; }
+    Event& operator=(Event&& o) noexcept {
+        std::swap(e, o.e);
+        return *this;
+    }
+    ~Event() {
+        if (e) (void)hipEventDestroy(e);
+    }
+    operator hipEvent_t() const { return e; }
+};
+
+template <typename T>
+struct PinnedBuf {  // page-locked host memory that only ever grows (contents are not kept)
+    T* ptr = nullptr;
+    size_t cap = 0;
+    void reserve(size_t n, unsigned flags = hipHostMallocDefault) {
+        if (n <= cap) return;
+        release();
+        const hipError_t r = hipHostMalloc(reinterpret_cast<void**>(&ptr), n * sizeof(T), flags);
+        if (r != hipSuccess) ptr = nullptr;
+        SH_HIP(r);
+        cap = n;
+    }
+    void release() {
+        if (ptr) (void)hipHostFree(ptr);
+        ptr = nullptr;
+        cap = 0;
+    }
+    ~PinnedBuf() { release(); }
+    PinnedBuf() = default;
+    PinnedBuf(PinnedBuf&& o) noexcept : ptr(o.ptr), cap(o.cap) { o.ptr = nullptr; o.cap = 0; }
+    PinnedBuf& operator=(PinnedBuf&& o) noexcept {
+        std::swap(ptr, o.ptr);
+        std::swap(cap, o.cap);
         return *this;
     }
 };

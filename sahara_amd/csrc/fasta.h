@@ -219,9 +219,12 @@ inline FastaData parseFastaParallel(const std::string& path, uint32_t sigma, uns
         std::thread t;
         uint8_t* p = nullptr;
         const CodesAlloc* a = nullptr;
-        uint8_t* take() {  // joined; the buffer is the caller's from here on
+        uint8_t* get() {  // joined; still released here if the parse fails
             if (t.joinable()) t.join();
-            uint8_t* q = p;
+            return p;
+        }
+        uint8_t* take() {  // the buffer is the caller's from here on
+            uint8_t* q = get();
             p = nullptr;
             return q;
         }
@@ -308,9 +311,11 @@ inline FastaData parseFastaParallel(const std::string& path, uint32_t sigma, uns
     if (!codes) {
         D.ranks.resize(base[P]);
     } else {
-        D.codes = ext.take();
-        if (!D.codes) D.ranks.resize((base[P] + 3) / 4);
-        out = D.codes ? D.codes : D.ranks.data();
+        out = ext.get();
+        if (!out) {
+            D.ranks.resize((base[P] + 3) / 4);
+            out = D.ranks.data();
+        }
         D.codesBytes = (base[P] + 3) / 4;
     }
     // per character: bits 0-1 its 2-bit code (A C G T = 0 1 2 3, N and
@@ -429,6 +434,7 @@ inline FastaData parseFastaParallel(const std::string& path, uint32_t sigma, uns
             D.badId.assign(b + h, eol - h);
             break;
         }
+    D.codes = ext.take();  // only now: a throw above releases the buffer
     return D;
 }
 

@@ -568,15 +568,13 @@ void buildFromParts(DeviceIndex& I, uint32_t sigma, uint64_t n, const uint64_t* 
     struct Phases {
         bool on = std::getenv("SAHARA_TIMING") != nullptr;
         hipStream_t st;
-        std::vector<std::pair<const char*, hipEvent_t>> ev;
+        std::vector<std::pair<const char*, Event>> ev;
         std::vector<double> host;
         std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
         void operator()(const char* what) {
             if (!on) return;
-            hipEvent_t e;
-            SH_HIP(hipEventCreate(&e));
-            SH_HIP(hipEventRecord(e, st));
-            ev.emplace_back(what, e);
+            ev.emplace_back(what, Event(hipEventDefault));
+            SH_HIP(hipEventRecord(ev.back().second, st));
             host.push_back(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
         }
         void report() {
@@ -589,9 +587,6 @@ void buildFromParts(DeviceIndex& I, uint32_t sigma, uint64_t n, const uint64_t* 
                 std::fprintf(stderr, " %s %.1f | %.1f", ev[i].first, ms, host[i] - host[i - 1]);
             }
             std::fprintf(stderr, "\n");
-        }
-        ~Phases() {
-            for (auto& x : ev) (void)hipEventDestroy(x.second);
         }
     } phase{};
     phase.st = st;
@@ -635,20 +630,13 @@ void buildFromParts(DeviceIndex& I, uint32_t sigma, uint64_t n, const uint64_t* 
     SH_HIP(hipGetLastError());
     phase("text");
     {
-        struct Side {  // the reverse BWT's upload stream and the event st waits on
-            hipStream_t s = nullptr;
-            hipEvent_t e = nullptr;
-            ~Side() {
-                if (e) (void)hipEventDestroy(e);
-                if (s) (void)hipStreamDestroy(s);
-            }
-        } side;
-        SH_HIP(hipStreamCreateWithFlags(&side.s, hipStreamNonBlocking));
-        SH_HIP(hipEventCreateWithFlags(&side.e, hipEventDisableTiming));
+        // the reverse BWT's upload stream and the event st waits on
+        Stream side(hipStreamNonBlocking);
+        Event sideUp(hipEventDisableTiming);
         bwtRev.reserve(n + 64);
-        upload(bwtRev.ptr, bwtR, n, side.s);
-        SH_HIP(hipEventRecord(side.e, side.s));
-        SH_HIP(hipStreamWaitEvent(st, side.e, 0));
+        upload(bwtRev.ptr, bwtR, n, side);
+        SH_HIP(hipEventRecord(sideUp, side));
+        SH_HIP(hipStreamWaitEvent(st, sideUp, 0));
         phase("bwtR up (beside the walks)");
         buildLines(bwtRev.ptr, n, nullptr, I.occR, totalsR, st);
         phase("occR");

@@ -45,63 +45,49 @@ DeviceIndex& partOf(Ctx* c, uint32_t p) { return p == 0 ? c->I : c->more.at(p - 
 // host after the last part (no per-batch sink).
 void run(Ctx* c, bool count) {
     if (c->more.empty()) return runOne(c, count);
-    sahara_hit* sink = c->sink;
-    c->sink = nullptr;
+    const ScopeExit sinkBack([c, sink = c->sk.sink] { c->sk.sink = sink; });
+    c->sk.sink = nullptr;
     sahara_stats T{};
     uint64_t total = 0;
     const auto t0 = std::chrono::steady_clock::now();
-    try {
-        for (uint32_t p = 0; p <= c->more.size(); ++p) {
-            if (p) std::swap(c->I, c->more[p - 1]);
-            try {
-                runOne(c, count);
-            } catch (...) {
+    for (uint32_t p = 0; p <= c->more.size(); ++p) {
+        if (p) std::swap(c->I, c->more[p - 1]);
+        {
+            const ScopeExit partBack([c, p] {
                 if (p) std::swap(c->I, c->more[p - 1]);
-                throw;
-            }
-            if (p) std::swap(c->I, c->more[p - 1]);
-            if (c->outAll.cap < total + c->nout) {  // grow, keeping the parts so far
-                DevBuf<sahara_hit> grown;
-                grown.reserve(std::max<uint64_t>((total + c->nout) + (total + c->nout) / 4, 1024));
-                if (total)
-                    SH_HIP(hipMemcpyAsync(grown.ptr, c->outAll.ptr, total * sizeof(sahara_hit), hipMemcpyDeviceToDevice,
-                                          c->st));
-                SH_HIP(hipStreamSynchronize(c->st));
-                c->outAll = std::move(grown);
-            }
-            launchOffsetSeq(c->out.ptr, c->nout, c->partRec0[p], c->outAll.ptr + total, c->st);
-            total += c->nout;
-            const sahara_stats& S = c->stats;  // the parts' work adds up
-            T.patterns = S.patterns;
-            T.search_grid = S.search_grid;
-            T.text_grid = S.text_grid;
-            T.pipelined = S.pipelined;
-            for (uint64_t sahara_stats::*f :
-                 {&sahara_stats::batches, &sahara_stats::cursors, &sahara_stats::nodes, &sahara_stats::rank_nodes,
-                  &sahara_stats::ext_lines, &sahara_stats::lf_steps, &sahara_stats::text_nodes,
-                  &sahara_stats::conversions, &sahara_stats::fm_iterations, &sahara_stats::text_iterations,
-                  &sahara_stats::text_active, &sahara_stats::text_refills, &sahara_stats::text_cycles_refill,
-                  &sahara_stats::text_cycles_step, &sahara_stats::text_cycles_emit, &sahara_stats::text_compare_steps,
-                  &sahara_stats::text_steps, &sahara_stats::text_launches,
-                  &sahara_stats::text_pos_tasks, &sahara_stats::text_stolen})
-                T.*f += S.*f;
-            for (double sahara_stats::*f : {&sahara_stats::search_ms, &sahara_stats::locate_ms, &sahara_stats::sort_ms,
-                                            &sahara_stats::text_ms, &sahara_stats::seed_ms})
-                T.*f += S.*f;
-            T.search_launches += S.search_launches;
+            });
+            runOne(c, count);
         }
-        if (c->out.cap < total) {
-            c->out.release();
-            c->out.reserve(std::max<uint64_t>(total, 1024));
-        }
-        sortHitsByQid(c->outAll.ptr, total, c->npat, c->out.ptr, c->merge, c->tmp, c->st);
-        SH_HIP(hipStreamSynchronize(c->st));
-    } catch (...) {
-        c->sink = sink;
-        throw;
+        if (c->outAll.cap < total + c->nout)  // grow, keeping the parts so far
+            c->outAll.growKeeping(std::max<uint64_t>((total + c->nout) + (total + c->nout) / 4, 1024), total, c->st);
+        launchOffsetSeq(c->out.ptr, c->nout, c->partRec0[p], c->outAll.ptr + total, c->st);
+        total += c->nout;
+        const sahara_stats& S = c->stats;  // the parts' work adds up
+        T.patterns = S.patterns;
+        T.search_grid = S.search_grid;
+        T.text_grid = S.text_grid;
+        T.pipelined = S.pipelined;
+        for (uint64_t sahara_stats::*f :
+             {&sahara_stats::batches, &sahara_stats::cursors, &sahara_stats::nodes, &sahara_stats::rank_nodes,
+              &sahara_stats::ext_lines, &sahara_stats::lf_steps, &sahara_stats::text_nodes,
+              &sahara_stats::conversions, &sahara_stats::fm_iterations, &sahara_stats::text_iterations,
+              &sahara_stats::text_active, &sahara_stats::text_refills, &sahara_stats::text_cycles_refill,
+              &sahara_stats::text_cycles_step, &sahara_stats::text_cycles_emit, &sahara_stats::text_compare_steps,
+              &sahara_stats::text_steps, &sahara_stats::text_launches,
+              &sahara_stats::text_pos_tasks, &sahara_stats::text_stolen})
+            T.*f += S.*f;
+        for (double sahara_stats::*f : {&sahara_stats::search_ms, &sahara_stats::locate_ms, &sahara_stats::sort_ms,
+                                        &sahara_stats::text_ms, &sahara_stats::seed_ms})
+            T.*f += S.*f;
+        T.search_launches += S.search_launches;
     }
-    c->sink = sink;
-    c->sinkDone = 0;
+    if (c->out.cap < total) {
+        c->out.release();
+        c->out.reserve(std::max<uint64_t>(total, 1024));
+    }
+    sortHitsByQid(c->outAll.ptr, total, c->npat, c->out.ptr, c->merge, c->tmp, c->st);
+    SH_HIP(hipStreamSynchronize(c->st));
+    c->sk.done = 0;
     c->nout = total;
     T.hits = total;
     T.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -111,7 +97,7 @@ void run(Ctx* c, bool count) {
 }
 
 void runOne(Ctx* c, bool count) {
-    if (!c->staged) throw Error("sahara_gpu_run: nothing staged");
+    if (!c->sk.staged) throw Error("sahara_gpu_run: nothing staged");
     auto t0 = std::chrono::steady_clock::now();
     // SAHARA_PIPELINE=0 (profiling hook): batch after batch on one stream, so
     // that a kernel trace shows each kernel's stand-alone duration
@@ -198,10 +184,10 @@ void runPass(Ctx* c, bool count, bool serial, sahara_stats& S, bool& overflow) {
     // 584-615M -> 668-689M reads/s, profiles/r03_pcie_batch_sweep.txt),
     // fewer for schemes with many searches (work items must fit 2^31);
     // SAHARA_BATCH sets it (tests of the pipeline)
-    uint64_t maxBatch = std::min<uint64_t>(c->streaming ? 1ull << 21 : 1ull << 22, (1ull << 31) / c->nsearch);
+    uint64_t maxBatch = std::min<uint64_t>(c->sk.streaming ? 1ull << 21 : 1ull << 22, (1ull << 31) / c->nsearch);
     if (const char* e = std::getenv("SAHARA_BATCH"))
         maxBatch = std::max<uint64_t>(1, std::min<uint64_t>((1ull << 31) / c->nsearch, std::atoll(e)));
-    if (c->blockRecs) maxBatch = std::min<uint64_t>(maxBatch, 1ull << 27);  // compact records: qid - q0 < 2^28
+    if (c->sk.blockRecs) maxBatch = std::min<uint64_t>(maxBatch, 1ull << 27);  // compact records: qid - q0 < 2^28
     const uint64_t batchesHere = (c->npat + maxBatch - 1) / maxBatch;
     if (!serial && batchesHere > 1 && c->verify) bpc = 1;
     if (const char* e = std::getenv("SAHARA_FM_BPC")) bpc = std::max(1, std::min(searchBlocksPerCU(sigma, c->edit, lds), std::atoi(e)));
@@ -263,7 +249,7 @@ void runPass(Ctx* c, bool count, bool serial, sahara_stats& S, bool& overflow) {
     // lost: C5 89.9M, C2 475M; profiles/r04_chunk_seeds_ab.txt).
     // SAHARA_CHUNK_SEEDS=0: one seed launch per batch
     const char* csEnv = std::getenv("SAHARA_CHUNK_SEEDS");
-    const bool chunkSeeds = c->streaming && !serial && split && !(csEnv && std::atoi(csEnv) == 0);
+    const bool chunkSeeds = c->sk.streaming && !serial && split && !(csEnv && std::atoi(csEnv) == 0);
     const bool early = !serial && split && (batchesHere > 1 || chunkSeeds);
     const bool chunked0 = early && chunkSeeds;
     const uint32_t textBlocks = (uint32_t)(c->numCU * std::max(tbpc, 1));
@@ -303,12 +289,7 @@ void runPass(Ctx* c, bool count, bool serial, sahara_stats& S, bool& overflow) {
     // counts (10, 11) and the rows --max_hits keeps (12-13). Pinned, so that their copies are plain DMA writes: a
     // copy into pageable memory waited behind the streamed upload's copies
     // (4.5 ms for batch 0's row total at C3 over PCIe, r3)
-    if (c->pinnedCap < nbatch * 16) {
-        if (c->pinned) SH_HIP(hipHostFree(c->pinned));
-        c->pinned = nullptr;
-        c->pinnedCap = nbatch * 16;
-        SH_HIP(hipHostMalloc(&c->pinned, c->pinnedCap * sizeof(uint32_t)));
-    }
+    c->pinned.reserve(nbatch * 16);
     if (c->qoff.cap < maxBatch + 1) {
         c->qoff.reserve(maxBatch + 1);
         c->big.reserve(maxBatch);
@@ -340,8 +321,8 @@ void runPass(Ctx* c, bool count, bool serial, sahara_stats& S, bool& overflow) {
         SH_HIP(hipMemsetAsync(c->counters.ptr + 38, 0xFF, sizeof(unsigned long long), sA));
     }
     c->nout = 0;
-    c->sinkDone = 0;
-    c->sinkOk = c->sink != nullptr || c->blockRecs != nullptr;
+    c->sk.done = 0;
+    c->sk.ok = c->sk.sink != nullptr || c->sk.blockRecs != nullptr;
     c->batchQ0.clear();
     c->batchEnd.clear();
     // a slot's counters and queues are zero when its `free` event fires:
@@ -457,11 +438,7 @@ void runPass(Ctx* c, bool count, bool serial, sahara_stats& S, bool& overflow) {
             for (uint64_t p0 = p1; p0 < bstart[1]; p0 += step, ++part) {
                 const uint64_t pe = std::min<uint64_t>(bstart[1], p0 + step);
                 ensureUploaded(c, pe, sD);
-                while (c->partEv.size() < 2 * (size_t)(part + 1)) {
-                    hipEvent_t e;
-                    SH_HIP(hipEventCreate(&e));
-                    c->partEv.push_back(e);
-                }
+                while (c->partEv.size() < 2 * (size_t)(part + 1)) c->partEv.emplace_back(hipEventDefault);
                 SH_HIP(hipEventRecord(c->partEv[2 * part], sD));
                 seeds((uint32_t)(p0 * c->nsearch), (uint32_t)(pe * c->nsearch));
                 SH_HIP(hipEventRecord(c->partEv[2 * part + 1], sD));
@@ -557,7 +534,7 @@ void runPass(Ctx* c, bool count, bool serial, sahara_stats& S, bool& overflow) {
     uint32_t seenTask = 0, seenHit = 0;  // pipelined overflow: the caps the re-run needs
     // a streamed call's finisher sleeps in its waits while the calling thread
     // and the pool pack (device-resident runs spin)
-    const bool sleepy = c->streaming && !serial;
+    const bool sleepy = c->sk.streaming && !serial;
     uint32_t pollUs = 20;
     if (const char* e = std::getenv("SAHARA_POLL_US")) pollUs = (uint32_t)std::max(0, std::atoi(e));
     unsigned long timerSlackNs = 1000;  // the finisher's timer slack (0: the process default)
@@ -580,7 +557,7 @@ void runPass(Ctx* c, bool count, bool serial, sahara_stats& S, bool& overflow) {
         c->partial.reserve(scanTiles((uint32_t)nb));
         querySegments(sl.qcnt.ptr, (uint32_t)nb, c->qoff.ptr, c->partial.ptr, c->big.ptr, c->small.ptr + 4, c->huge.ptr,
                       c->small.ptr + 5, sC);
-        uint32_t* pr = c->pinned + b * 16;
+        uint32_t* pr = c->pinned.ptr + b * 16;
         launchBatchTotals(sl.small.ptr, c->qoff.ptr + nb, c->small.ptr + 4, pr, sC);
         SH_HIP(hipEventRecord(sleepy ? c->evSleep[0] : c->ev[6], sC));
         if (sleepy) waitSleepy(c->evSleep[0], pollUs);
@@ -650,31 +627,23 @@ void runPass(Ctx* c, bool count, bool serial, sahara_stats& S, bool& overflow) {
         resetSlot(sl, sC);  // the slot's hits are consumed
         if (nhuge) c->tmp.reserve(bigSortTempBytes(rows, nhuge) + 256);
         if (c->nout + rows > c->out.cap) {  // grow the device-resident output
-            const size_t want = std::max<size_t>((c->nout + rows) + (c->nout + rows) / 2, 1024);
-            sahara_hit* np = nullptr;
-            SH_HIP(hipMalloc(&np, want * sizeof(sahara_hit)));
-            if (c->nout) SH_HIP(hipMemcpyAsync(np, c->out.ptr, c->nout * sizeof(sahara_hit), hipMemcpyDeviceToDevice, sC));
-            SH_HIP(hipStreamSynchronize(sC));
             SH_HIP(hipStreamSynchronize(c->stF));  // sink copies may still read the old buffer
-            c->out.release();
-            c->out.ptr = np;
-            c->out.base = np;
-            c->out.cap = want;
+            c->out.growKeeping(std::max<size_t>((c->nout + rows) + (c->nout + rows) / 2, 1024), c->nout, sC);
         }
         sortDecode(c->k0.ptr, c->k1.ptr, rows, c->qoff.ptr, (uint32_t)nb, c->big.ptr, nbig, hugeList, nhuge, q0,
                    c->I.dRecStarts.ptr, (uint32_t)c->I.recStarts.size(), c->out.ptr + c->nout, c->tmp.ptr, c->tmp.cap,
                    sC);
-        if (c->limitN)  // --max_hits: this batch's queries keep their n best positions (search_n)
-            rows = limitBatch(c->out.ptr + c->nout, rows, c->qoff.ptr, (uint32_t)nb, c->limitN, c->limitCnt,
+        if (c->sk.limitN)  // --max_hits: this batch's queries keep their n best positions (search_n)
+            rows = limitBatch(c->out.ptr + c->nout, rows, c->qoff.ptr, (uint32_t)nb, c->sk.limitN, c->limitCnt,
                               c->limitOff, c->limitBuf, c->tmp, reinterpret_cast<uint64_t*>(pr + 12), sC);
         SH_HIP(hipEventRecord(c->ev[4], sC));
         // sahara_gpu_search's host sink: the batch's hits go to host memory
         // on stF while later batches search (while they fit the sink)
         c->batchQ0.push_back(q0);
         c->batchEnd.push_back(c->nout + rows);
-        if (c->sinkOk && c->nout + rows <= c->sinkCap) {
-            const bool compact = c->compactSink && rows * sizeof(uint64_t) <= Ctx::kDownSlot && nb < (1ull << 28);
-            if (rows && c->blockRecs) {
+        if (c->sk.ok && c->nout + rows <= c->sk.cap) {
+            const bool compact = c->sk.compact && rows * sizeof(uint64_t) <= Ctx::kDownSlot && nb < (1ull << 28);
+            if (rows && c->sk.blockRecs) {
                 // compact records made in HBM on sC (full grid, ~20 us), then
                 // one D2H copy on stF: a copy engine moves them, no workgroup
                 // waits on PCIe writes beside the text phase
@@ -682,19 +651,14 @@ void runPass(Ctx* c, bool count, bool serial, sahara_stats& S, bool& overflow) {
                                   1u << 16);
                 SH_HIP(hipEventRecord(c->ev[7], sC));
                 SH_HIP(hipStreamWaitEvent(c->stF, c->ev[7], 0));
-                SH_HIP(hipMemcpyAsync(c->blockRecs + c->nout, c->outRecs.ptr + c->nout, rows * sizeof(uint64_t),
+                SH_HIP(hipMemcpyAsync(c->sk.blockRecs + c->nout, c->outRecs.ptr + c->nout, rows * sizeof(uint64_t),
                                       hipMemcpyDeviceToHost, c->stF));
             } else if (rows && compact) {  // 8-B records, expanded on the host (Expander)
-                const uint64_t j = c->downJobs++;
+                const uint64_t j = c->sk.downJobs++;
                 const size_t slot = (size_t)(j % Ctx::kDownSlots);
                 if (j >= Ctx::kDownSlots) c->expander->waitFor(j + 1 - Ctx::kDownSlots);  // the slot is read
-                if (c->downEv.size() <= slot) {
-                    const size_t had = c->downEv.size();
-                    c->downEv.resize(Ctx::kDownSlots);
-                    for (size_t i = had; i < Ctx::kDownSlots; ++i)
-                        SH_HIP(hipEventCreateWithFlags(&c->downEv[i], hipEventDisableTiming));
-                }
-                uint64_t* stage = c->downRing + slot * (Ctx::kDownSlot / sizeof(uint64_t));
+                while (c->downEv.size() < Ctx::kDownSlots) c->downEv.emplace_back(hipEventDisableTiming);
+                uint64_t* stage = c->downRing.ptr + slot * (Ctx::kDownSlot / sizeof(uint64_t));
                 c->outC.reserve(Ctx::kDownSlots * (Ctx::kDownSlot / sizeof(uint64_t)));
                 uint64_t* dev = c->outC.ptr + slot * (Ctx::kDownSlot / sizeof(uint64_t));
                 launchCompactHits(c->out.ptr + c->nout, rows, q0, c->I.dRecStarts.ptr, dev, sC);
@@ -702,19 +666,19 @@ void runPass(Ctx* c, bool count, bool serial, sahara_stats& S, bool& overflow) {
                 SH_HIP(hipStreamWaitEvent(c->stF, c->ev[7], 0));
                 SH_HIP(hipMemcpyAsync(stage, dev, rows * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stF));
                 SH_HIP(hipEventRecord(c->downEv[slot], c->stF));
-                c->expander->submit({c->downEv[slot], stage, c->sink + c->nout, rows, q0});
-            } else if (rows && c->sinkPinned) {
+                c->expander->submit({c->downEv[slot], stage, c->sk.sink + c->nout, rows, q0});
+            } else if (rows && c->sk.pinned) {
                 SH_HIP(hipStreamWaitEvent(c->stF, c->ev[4], 0));
-                SH_HIP(hipMemcpyAsync(c->sink + c->nout, c->out.ptr + c->nout, rows * sizeof(sahara_hit),
+                SH_HIP(hipMemcpyAsync(c->sk.sink + c->nout, c->out.ptr + c->nout, rows * sizeof(sahara_hit),
                                       hipMemcpyDeviceToHost, c->stF));
             } else if (rows) {  // neither fits: the rest goes after the pass
-                c->sinkOk = false;
+                c->sk.ok = false;
             }
-            if (c->sinkOk) c->sinkDone = c->nout + rows;
+            if (c->sk.ok) c->sk.done = c->nout + rows;
         } else {
-            c->sinkOk = false;
+            c->sk.ok = false;
         }
-        SH_HIP(hipMemcpyAsync(c->pinned + b * 16 + 7, c->small.ptr + 2, 4, hipMemcpyDeviceToHost, sC));
+        SH_HIP(hipMemcpyAsync(c->pinned.ptr + b * 16 + 7, c->small.ptr + 2, 4, hipMemcpyDeviceToHost, sC));
         SH_HIP(hipEventRecord(c->ev[5], sC));
         if (sleepy) SH_HIP(hipEventRecord(c->evSleep[2], sC));
         c->nout += rows;
@@ -724,7 +688,7 @@ void runPass(Ctx* c, bool count, bool serial, sahara_stats& S, bool& overflow) {
     auto finishCheck = [&](uint64_t b) {
         if (sleepy) waitSleepy(c->evSleep[2], pollUs);  // recorded beside ev[5]
         SH_HIP(hipEventSynchronize(c->ev[5]));
-        if (c->pinned[b * 16 + 7] & 4u) throw Error("locate walked off the SA samples (corrupt index)");
+        if (c->pinned.ptr[b * 16 + 7] & 4u) throw Error("locate walked off the SA samples (corrupt index)");
         float ms = 0;
         SH_HIP(hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
         S.locate_ms += ms;

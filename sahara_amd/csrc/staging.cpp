@@ -87,16 +87,10 @@ static bool stageIn(Ctx* c, uint8_t* dst, const uint8_t* src, size_t n) {
         return true;
     }
     const size_t nb = (n + 1) / 2;  // packed bytes
-    if (c->nibHostCap < nb) {
-        if (c->nibHost) SH_HIP(hipHostFree(c->nibHost));
-        c->nibHost = nullptr;
-        c->nibHostCap = 0;
-        SH_HIP(hipHostMalloc(reinterpret_cast<void**>(&c->nibHost), nb));
-        c->nibHostCap = nb;
-    }
+    c->nibHost.reserve(nb);
     c->nibPats.reserve(nb + 8);
     SH_HIP(hipStreamSynchronize(c->st));  // the pinned buffer may still feed the last call's DMA
-    uint8_t* out = c->nibHost;
+    uint8_t* out = c->nibHost.ptr;
     const unsigned nt = hostThreads(c, 16);
     constexpr size_t kPiece = 4u << 20;
     const size_t pieces = (nb + kPiece - 1) / kPiece;
@@ -405,7 +399,7 @@ static void runPieces(TaskPool& P, uint64_t n, const std::function<void(uint64_t
 // thread alone.
 void uploadViaRing(Ctx* c, void* dst, const void* src, size_t bytes, hipStream_t st) {
     if (c->ringInit.joinable()) c->ringInit.join();
-    if (!c->ring || bytes < Ctx::kRingSlot) {
+    if (!c->ring.ptr || bytes < Ctx::kRingSlot) {
         SH_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st));
         return;
     }
@@ -416,7 +410,7 @@ void uploadViaRing(Ctx* c, void* dst, const void* src, size_t bytes, hipStream_t
         const size_t slot = (size_t)(c->ringLoadNext++ % Ctx::kRingSlots);
         const size_t len = std::min(Ctx::kRingSlot, bytes - off);
         SH_HIP(hipEventSynchronize(c->ringEv[slot]));  // the slot's previous copy is done
-        uint8_t* stage = c->ring + slot * Ctx::kRingSlot;
+        uint8_t* stage = c->ring.ptr + slot * Ctx::kRingSlot;
         runPieces(P, (len + kPiece - 1) / kPiece, [&](uint64_t i) {
             std::memcpy(stage + i * kPiece, s + off + i * kPiece, std::min(kPiece, len - i * kPiece));
         });
@@ -445,7 +439,7 @@ static void submitPack(Ctx* c, uint64_t j) {
     J.chunk = j;
     J.pieceSyms = pieceSyms;
     J.bad.store(0, std::memory_order_relaxed);
-    uint8_t* out = c->ring + slot * Ctx::kRingSlot;
+    uint8_t* out = c->ring.ptr + slot * Ctx::kRingSlot;
     std::vector<std::function<void()>> fs;
     if (U.prepacked) {  // codes as given: the chunk's bytes of the caller's buffer, copied in pieces
         const uint64_t B0 = (U.sym0 + s0) / 4, nb = (U.sym0 + s0 + n + 3) / 4 - B0, pb = pieceSyms / 4;
@@ -482,7 +476,7 @@ static void submitPack(Ctx* c, uint64_t j) {
 // pool (2-bit upload), within the ring's slots.
 static void packAhead(Ctx* c) {
     Ctx::Upload& U = c->up;
-    if (!c->streaming || U.bits != 2 || U.bad) return;
+    if (!c->sk.streaming || U.bits != 2 || U.bad) return;
     const uint64_t doneChunks = U.done / U.chunk + (U.done % U.chunk ? 1 : 0);
     const uint64_t want = std::min({chunkCount(U), doneChunks + U.ahead, doneChunks + Ctx::kRingSlots - 1});
     while (U.submitted < want) submitPack(c, U.submitted);
@@ -498,10 +492,7 @@ void drainPacking(Ctx* c) {
 static void uploadCopy(Ctx* c, void* dst, const void* src, uint64_t bytes) {
     if (c->traceOn) {  // the DMA's own duration (printed with the marks)
         if (c->dmaUsed == c->dmaEv.size()) {
-            hipEvent_t a, b;
-            SH_HIP(hipEventCreate(&a));
-            SH_HIP(hipEventCreate(&b));
-            c->dmaEv.push_back({0, {a, b}});
+            c->dmaEv.emplace_back(0, std::make_pair(Event(hipEventDefault), Event(hipEventDefault)));
         }
         auto& d = c->dmaEv[c->dmaUsed++];
         d.first = bytes;
@@ -540,7 +531,7 @@ void uploadChunk(Ctx* c, hipStream_t kst) {
     uint64_t nExc = 0, excOff = 0;  // 2 bits: the N list, at byte excOff of the chunk's region
     const uint32_t* excDev = nullptr;  // ... on the device
     uint32_t so = 0;                   // read r0's first symbol in the chunk's first byte (prepacked)
-    uint8_t* out = c->ring + slot * Ctx::kRingSlot;
+    uint8_t* out = c->ring.ptr + slot * Ctx::kRingSlot;
     if (bits == 2 && U.prepacked) {
         if (U.submitted <= j) submitPack(c, j);
         c->packJobs[slot].group.wait();
@@ -630,7 +621,7 @@ void uploadChunk(Ctx* c, hipStream_t kst) {
 // device-side packing on stream kst (a no-op when the patterns were staged
 // whole).
 void ensureUploaded(Ctx* c, uint64_t patEnd, hipStream_t kst) {
-    if (!c->streaming) return;
+    if (!c->sk.streaming) return;
     Ctx::Upload& U = c->up;
     auto covered = [&] { return U.rc ? std::min(2 * U.done, c->npat) : U.done; };
     while (covered() < patEnd) {
@@ -742,7 +733,7 @@ static void stagePackedN(Ctx* c, const PackedReads& P, uint64_t rows, uint32_t m
 void stageStreamed(Ctx* c, const uint8_t* src, uint64_t rows, bool rc, uint64_t npat, uint32_t m,
                    const uint32_t* pi, const uint32_t* l, const uint32_t* u, uint32_t ns, int edit,
                    const PackedReads* packed) {
-    c->staged = c->streaming = false;
+    c->sk = {};  // a new call
     if (m == 0 || m > kMaxPatternLen) throw Error("pattern length out of range");
     if (packed && c->I.sigma != 5 && c->I.sigma != 6) throw Error("reads two bits per symbol need a dna4 or dna5 index");
     stageScheme(c, npat, m, pi, l, u, ns, edit);
@@ -792,18 +783,18 @@ void stageStreamed(Ctx* c, const uint8_t* src, uint64_t rows, bool rc, uint64_t 
     U.chunk = std::max<uint64_t>(step, chunk - chunk % step);
     if (packed) stagePackedN(c, *packed, rows, m);
     if (c->ringInit.joinable()) c->ringInit.join();
-    if (U.bits != 8 && !c->ring) throw Error("could not pin the upload ring buffer");
-    for (hipEvent_t e : c->ringEv) SH_HIP(hipEventSynchronize(e));  // the last call's DMAs
+    if (U.bits != 8 && !c->ring.ptr) throw Error("could not pin the upload ring buffer");
+    for (const Event& e : c->ringEv) SH_HIP(hipEventSynchronize(e));  // the last call's DMAs
     if (U.bits != 8) c->nibPats.reserve((rows * m + 1) / 2 + 16);  // + the 12 B the 2-bit packer's last loads may touch
     SH_HIP(hipMemsetAsync(c->badFlag.ptr, 0, sizeof(uint32_t), c->stE));
     c->stageMs = 0;
-    c->staged = c->streaming = true;
+    c->sk.staged = c->sk.streaming = true;
 }
 
 void stage(Ctx* c, const uint8_t* ranks, uint64_t npat, uint32_t m, const uint32_t* pi, const uint32_t* l,
            const uint32_t* u, uint32_t ns, int edit) {
     if (npat == 0) throw Error("no patterns");
-    c->staged = c->streaming = false;
+    c->sk = {};  // a new call
     std::vector<uint32_t> packed;
     packSchemeTable(pi, l, u, ns, m, packed, c->maxErr);  // a bad scheme fails before the upload
     if ((size_t)ns * m * 4 > 60 * 1024) throw Error("scheme too large for LDS (searches * len > 15360)");
@@ -813,10 +804,7 @@ void stage(Ctx* c, const uint8_t* ranks, uint64_t npat, uint32_t m, const uint32
     {
         DevBuf<uint8_t>& raw = c->rawPats;  // kept: no 2 GB allocate / free per call at C3
         raw.reserve(npat * m);
-        if (!stageIn(c, raw.ptr, ranks, npat * m)) {
-            c->staged = false;
-            throw Error("pattern rank out of range for this index");
-        }
+        if (!stageIn(c, raw.ptr, ranks, npat * m)) throw Error("pattern rank out of range for this index");
         c->pats.reserve(npat * c->patWords + 4);  // + tail words read by paired loads
         SH_HIP(hipMemsetAsync(c->small.ptr, 0, sizeof(uint32_t), c->st));
         launchPackPatterns(raw.ptr, npat, m, c->patWords, c->I.sigma, c->pats.ptr, c->small.ptr, c->st);
@@ -826,15 +814,12 @@ void stage(Ctx* c, const uint8_t* ranks, uint64_t npat, uint32_t m, const uint32
         uint32_t bad = 0;
         SH_HIP(hipMemcpyAsync(&bad, c->small.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, c->st));
         SH_HIP(hipStreamSynchronize(c->st));
-        if (bad) {
-            c->staged = false;
-            throw Error("pattern rank out of range for this index");
-        }
+        if (bad) throw Error("pattern rank out of range for this index");
     }
     stageScheme(c, npat, m, pi, l, u, ns, edit);
     c->npat = npat;
     c->m = m;
-    c->staged = true;
+    c->sk.staged = true;
     c->stageMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 

@@ -420,16 +420,23 @@ def test_search_reads_and_streamed_upload(gpu_device, monkeypatch, chunk, batch,
     assert np.array_equal(hits_as_rows(gpu.fetch()), fwd)
 
 
-@pytest.mark.parametrize("bad_value", [0, 6, 17])
-def test_streamed_upload_refuses_bad_rank_in_a_late_chunk(gpu_device, monkeypatch, bad_value):
+@pytest.mark.parametrize("bad_value,pin_min", [pytest.param(0, None, id="0"), pytest.param(6, None, id="6"),
+                                               pytest.param(17, None, id="17"), pytest.param(6, "0", id="6-pinned")])
+def test_streamed_upload_refuses_bad_rank_in_a_late_chunk(gpu_device, monkeypatch, bad_value, pin_min):
     """A byte that is no rank (0, >= sigma) in a chunk uploaded while earlier
     batches already search: the call fails loudly, nothing of the bad chunk is
-    searched, and the context serves the next call."""
+    searched, and the context serves the next call. The failing calls' hits
+    were on their way into pageable memory through the expander, or (pinned:
+    SAHARA_PIN_MIN=0, after a first call, since a context's first call pins
+    nothing) straight into a page-locked sink."""
     monkeypatch.setenv("SAHARA_UPLOAD_CHUNK", "64")
     monkeypatch.setenv("SAHARA_BATCH", "97")
     flat, lens, reads, pats, sch, ref = _streamed_inputs()
     want = hits_as_rows(ref.search(pats, sch, nthreads=8)[0])
     gpu = sa.BiFMIndex.build_flat(flat, lens, sigma=6, device=gpu_device)
+    if pin_min is not None:
+        monkeypatch.setenv("SAHARA_PIN_MIN", pin_min)
+        assert np.array_equal(hits_as_rows(sa.search_reads(gpu, reads, sch)), want)
     bad = reads.copy()
     bad[1900, 5] = bad_value
     with pytest.raises(sa.SaharaError, match="out of range"):

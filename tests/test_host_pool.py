@@ -1,0 +1,16 @@
+"""The context's host thread pools under the thread and address sanitizers (CPU)."""
+import os
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.mark.parametrize("sanitize", ["thread", "address,undefined"])
+def test_host_pools_are_clean_under_sanitizers(tmp_path, sanitize):
+    exe = tmp_path / "host_pool_check"
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-pthread", "-fsanitize=" + sanitize,
+                    os.path.join(ROOT, "tests", "host_pool_check.cpp"), "-o", str(exe)], check=True)
+    p = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0 and p.stderr == "", (p.returncode, p.stderr[-4000:])
