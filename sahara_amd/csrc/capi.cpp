@@ -180,8 +180,10 @@ Ctx* newCtx(int device) {
     // (No stream gets a CU mask: with a CU-masked stream in the process the
     // memory-bound kernels on the other streams ran 1.4-1.8x longer, r5.)
     for (Stream* s : {&c->st, &c->stB, &c->stC, &c->stD, &c->stE, &c->stF}) *s = Stream(hipStreamNonBlocking);
-    for (auto& e : c->ev) e = Event(hipEventDefault);
-    for (auto& e : c->evSleep) e = Event(hipEventDisableTiming | hipEventBlockingSync);
+    for (Event* e : {&c->outCopied[0], &c->outCopied[1], &c->locStart, &c->locDone, &c->sortDone, &c->totalsDown,
+                     &c->flagsDown, &c->recsMade})
+        *e = Event(hipEventDefault);
+    for (Event* e : {&c->totalsDownSleep, &c->flagsDownSleep}) *e = Event(hipEventDisableTiming | hipEventBlockingSync);
     for (auto& e : c->ringEv) e = Event(hipEventDisableTiming);
     // the streamed upload's pinned ring, pinned while the caller builds or
     // loads the index (pinning 256 MB takes ~50 ms)
@@ -203,8 +205,8 @@ Ctx* newCtx(int device) {
         for (Event* e : {&sl.fmStart, &sl.seedDone, &sl.seedDone0, &sl.seedMid, &sl.fmBegin, &sl.fmDone, &sl.textStart,
                          &sl.textDone, &sl.free, &sl.textMid0, &sl.textMid1})
             *e = Event(hipEventDefault);
-        sl.small.reserve(8);
-        sl.queues.reserve(768);
+        sl.small.reserve(kSlotWords);
+        sl.queues.reserve(kQueuesWords);
     }
     for (auto& p : c->outStage) p.reserve(Ctx::kOutChunk);
     c->small.reserve(8);
@@ -620,10 +622,10 @@ static void copyOut(Ctx* c, void* dst, const void* src, size_t bytes) {
         if (k < n) {
             SH_HIP(hipMemcpyAsync(c->outStage[k & 1].ptr, static_cast<const char*>(src) + k * Ctx::kOutChunk, len(k),
                                   hipMemcpyDeviceToHost, c->st));
-            SH_HIP(hipEventRecord(c->ev[k & 1], c->st));
+            SH_HIP(hipEventRecord(c->outCopied[k & 1], c->st));
         }
         if (k > 0) {
-            SH_HIP(hipEventSynchronize(c->ev[(k - 1) & 1]));
+            SH_HIP(hipEventSynchronize(c->outCopied[(k - 1) & 1]));
             parallelCopy(static_cast<char*>(dst) + (k - 1) * Ctx::kOutChunk, c->outStage[(k - 1) & 1].ptr, len(k - 1));
         }
     }
@@ -971,25 +973,17 @@ int sahara_gpu_prepare(void* ctx, uint64_t n_patterns, uint32_t len) {
         if (!c) return;  // (NULL context: the host part only, e.g. beside the index load)
         if (pinned) c->outRecs.reserve(capBytes / 8);
         c->out.reserve(est);
-        // the slots of a streamed pass (pass.cpp runPass: 2M-pattern batches),
-        // sized as that pass sizes them
-        const uint64_t maxBatch = 1ull << 21;
-        initWorkCaps(c, maxBatch);
+        // the slots and the locate chain's buffers of a streamed pass, from
+        // the pass's own sizing (pass.cpp; the keys sized for a batch's rows
+        // at four per pattern, grown by the pass if short)
+        const PassKnobs k = readPassKnobs(c->verify);
+        const uint64_t maxBatch = maxBatchOf(std::nullopt, true, 1, false);
+        initWorkCaps(c, maxBatch, k);
         const uint64_t nb = std::min<uint64_t>((n_patterns + maxBatch - 1) / maxBatch, Ctx::kSlots);
-        // the locate chain's per-batch buffers (pass.cpp; the keys sized for a
-        // batch's rows at four per pattern, grown by the pass if short)
-        c->qoff.reserve(maxBatch + 1);
-        c->big.reserve(maxBatch);
-        c->huge.reserve(maxBatch);
+        reserveLocate(c, maxBatch, nb);
         c->partial.reserve(scanTiles((uint32_t)maxBatch));
         c->k0.reserve(std::min<uint64_t>(n_patterns, maxBatch) * 4);
-        for (uint64_t i = 0; i < nb; ++i) {
-            Ctx::Slot& sl = c->slot[i];
-            sl.hits.reserve((size_t)c->hitCap + 1);
-            sl.rank.reserve((size_t)c->hitCap + 1);
-            sl.tasks.reserve((size_t)c->taskCap);
-            sl.qcnt.reserve(maxBatch + 1);  // per-query row counts (pass.cpp)
-        }
+        for (uint64_t i = 0; i < nb; ++i) reserveSlot(c, c->slot[i]);
         if (len) {
             const uint64_t patWords = (len + 7) / 8, patBlocks = (len + 31) / 32;
             c->rawPats.reserve(n_patterns * len);

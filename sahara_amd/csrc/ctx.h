@@ -18,6 +18,7 @@
 #include "../../include/sahara_hip.h"
 #include "device_index.h"
 #include "host_pool.h"
+#include "pass_plan.h"
 #include "search.h"
 
 namespace sahara {
@@ -146,11 +147,6 @@ private:
     std::exception_ptr err_;
 };
 
-// Text-phase scheduling defaults (SAHARA_TEXT_STEPS / SAHARA_REFILL_AT override
-// them per pass). Two micro-steps per iteration beat four by 5% on C3 and 2% on
-// C5, C2 within noise (profiles/r05_text_steps_ab.txt).
-constexpr uint32_t kTextStepsDefault = 2;
-constexpr uint32_t kRefillAtDefault = 8;
 // Ownership and teardown. Every handle of a context has an owning type
 // (DevBuf, Stream, Event, PinnedBuf, unique_ptr), so ~Ctx releases nothing by
 // hand: it only ends the host threads, in the order pinning thread, expander,
@@ -187,12 +183,8 @@ struct Ctx {
     bool edit = true;
     bool verify = true;
     bool locateSA = true;
-    uint32_t split = 1;                   // text-phase threshold (rows per interval)
-    uint32_t textSteps = kTextStepsDefault;  // text-phase micro-steps per lane per wave iteration
-    uint32_t refillAt = kRefillAtDefault;    // text-phase batch refill threshold (idle lanes)
 
-    bool pipeline = true;
-    DevBuf<uint4> stack;                  // FM spill stack (stream st only)
+    DevBuf<uint4> stack;                 // FM spill stack (stream st only)
     DevBuf<uint8_t> rawPats;              // staged pattern bytes before packing
     DevBuf<uint8_t> nibPats;              // the same, two symbols per byte as uploaded (stageIn)
     bool nibbleUpload = true;             // SAHARA_NIBBLE_UPLOAD=0: pattern bytes go up as given
@@ -325,9 +317,8 @@ struct Ctx {
         DevBuf<uint32_t> seedItem;
         DevBuf<uint32_t> qcnt, rank;      // rows ranked at emission: per-query row counts (zero between
                                           // batches), per hit slot its first row's place in its segment
-        DevBuf<uint32_t> small;           // -, hitCount, flags, filled, taskCount, seed tasks, seedCount
-        DevBuf<uint32_t> queues;          // striped work counters: FM seeds [0, 256), text tasks: the seed
-                                          // tasks [256, 512), the FM phase's [512, 768)
+        DevBuf<uint32_t> small;           // the slot's counters, by SlotWord (search.h)
+        DevBuf<uint32_t> queues;          // striped work counters, three queues at QueueAt (search.h)
         // kernel spans, each recorded on the kernel's own stream right around
         // its launch(es): seeds fmStart..seedDone (sD), FM fmBegin..fmDone
         // (sA), text textStart..textDone (sB); seedDone0: the batch's first
@@ -345,18 +336,22 @@ struct Ctx {
     // (the rule at the top of Ctx).
     Stream st, stB, stC, stD;  // FM phase and single-stream work; text, locate / sort, seeds
     Stream stE, stF;           // pattern upload; hit download (sink)
-    Event ev[8];
-    // the finisher's waits in a streamed call (text done, row total, batch
-    // checked): blocking-sync events, so that it sleeps instead of spinning a
-    // CPU that the packing threads need (a 16-CPU quota on the GPU box)
-    Event evSleep[3];
+    Event outCopied[2];        // capi.cpp copyOut: a staging chunk's DMA is done
+    // a batch's locate chain on stC (pass.cpp finish): its start, locate and
+    // sort + decode done (timing), the batch's totals and its locate flags
+    // in the pinned record, its compact records made
+    Event locStart, locDone, sortDone, totalsDown, flagsDown, recsMade;
+    // the finisher's waits in a streamed call, recorded in place of totalsDown
+    // and beside flagsDown: blocking-sync events, so that it sleeps instead of
+    // spinning a CPU that the packing threads need (a 16-CPU quota on the GPU box)
+    Event totalsDownSleep, flagsDownSleep;
     std::vector<Event> partEv;  // around the first batch's later seed launches (created on demand)
     Event ringEv[kRingSlots];
     std::vector<Event> downEv;
     // SAHARA_TIMING=2: timing events around each chunk's DMA (bytes, events)
     std::vector<std::pair<uint64_t, std::pair<Event, Event>>> dmaEv;
     size_t dmaUsed = 0;
-    PinnedBuf<uint32_t> pinned;           // host copies of the slots' small counters (16 u32 per batch)
+    PinnedBuf<BatchRecord> pinned;        // per batch: host copies of its slot's counters and totals
     // two pinned staging chunks for handing hits to pageable host memory: the
     // DMA of one chunk overlaps the host copy out of the other (copyOut)
     static constexpr size_t kOutChunk = 32u << 20;
@@ -452,6 +447,10 @@ void run(Ctx* c, bool count);
 void runOne(Ctx* c, bool count);
 void runPass(Ctx* c, bool count, bool serial, sahara_stats& S, bool& overflow);
 void growCap(uint32_t& cap, uint32_t seen);
-void initWorkCaps(Ctx* c, uint64_t maxBatch);
+// the buffers of a pass with batches of maxBatch patterns, as the pass sizes
+// them (sahara_gpu_prepare makes them ahead of the first call)
+void initWorkCaps(Ctx* c, uint64_t maxBatch, const PassKnobs& k);
+void reserveSlot(Ctx* c, Ctx::Slot& sl);
+void reserveLocate(Ctx* c, uint64_t maxBatch, uint64_t nslots);
 
 }  // namespace sahara

@@ -9,6 +9,7 @@
 #include <condition_variable>
 #include <cstdint>
 #include <deque>
+#include <exception>
 #include <functional>
 #include <mutex>
 #include <thread>
@@ -178,5 +179,75 @@ struct TaskGroup {
         cv.wait(lk, [&] { return left == 0; });
     }
 };
+
+// The issuer / finisher handshake of a pipelined pass (pass.cpp runPass). The
+// calling thread runs issue(b) for b = 0 .. n-1, never more than `window`
+// batches ahead of the last finished one; a second thread runs setup(), then
+// finish(f) in order, each after issue(f) has returned, then trail() once. A
+// finish that returns false stops both sides (the pass overflowed). An
+// exception on either side stops the other and is rethrown here after the
+// join, the issuer's if both threw. afterJoin() runs on the calling thread
+// between the join and the rethrow (the pass waits for its streams there).
+template <class Setup, class Issue, class Finish, class Trail, class AfterJoin>
+void issueAndFinish(uint64_t n, uint64_t window, Setup&& setup, Issue&& issue, Finish&& finish, Trail&& trail,
+                    AfterJoin&& afterJoin) {
+    std::mutex mu;
+    std::condition_variable cv;
+    uint64_t issued = 0, released = 0;  // batches issued; batches finished
+    bool stop = false;
+    std::exception_ptr finErr, issueErr;
+    std::thread finisher([&] {
+        try {
+            setup();
+            for (uint64_t f = 0; f < n; ++f) {
+                {
+                    std::unique_lock<std::mutex> lk(mu);
+                    cv.wait(lk, [&] { return issued > f || stop; });
+                    if (issued <= f) break;
+                }
+                const bool go = finish(f);
+                {
+                    std::lock_guard<std::mutex> g(mu);
+                    released = f + 1;
+                    if (!go) stop = true;
+                }
+                cv.notify_all();
+                if (!go) break;
+            }
+            trail();
+        } catch (...) {
+            finErr = std::current_exception();
+        }
+        std::lock_guard<std::mutex> g(mu);
+        stop = true;
+        cv.notify_all();
+    });
+    try {
+        for (uint64_t b = 0; b < n; ++b) {
+            {
+                std::unique_lock<std::mutex> lk(mu);
+                cv.wait(lk, [&] { return b < released + window || stop; });
+                if (stop) break;
+            }
+            issue(b);
+            {
+                std::lock_guard<std::mutex> g(mu);
+                issued = b + 1;
+            }
+            cv.notify_all();
+        }
+    } catch (...) {
+        issueErr = std::current_exception();
+    }
+    {
+        std::lock_guard<std::mutex> g(mu);
+        if (issueErr) stop = true;
+    }
+    cv.notify_all();
+    finisher.join();
+    afterJoin();
+    if (issueErr) std::rethrow_exception(issueErr);
+    if (finErr) std::rethrow_exception(finErr);
+}
 
 }  // namespace sahara

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 
 #include "../../include/sahara_hip.h"
@@ -33,8 +34,8 @@ struct SearchArgs {
     uint32_t hitCap;
     uint32_t* hitCount;      // reserved slots (waves reserve ranges; unused slots have len 0)
     uint32_t* filled;        // records actually written
-    uint32_t* flags;         // 1 stack, 2 hits, 4 locate, 8 tasks, 16 text window
-    unsigned long long* counters;  // nodes, rank nodes, lines, lf steps, digest, text nodes, tasks
+    uint32_t* flags;         // Flag bits
+    unsigned long long* counters;  // by Counter
     uint4* tasks;            // text tasks (row, |t|, qid, meta | search << 24)
     uint32_t taskCap;
     uint32_t* taskCount;
@@ -68,19 +69,65 @@ struct SeedArgs {
     uint4* tasks;
     uint32_t taskCap;
     uint32_t* taskCount;
-    uint32_t* flags;            // 8: task buffer too small
-    unsigned long long* counters;  // count mode: text tasks (+6), else nullptr
+    uint32_t* flags;            // kFlagTasks: task buffer too small
+    unsigned long long* counters;  // count mode: text tasks (kCtTextTasks), else nullptr
 };
 
-// Text phase LDS: the scheme table comes first and takes at least one block of
-// lane words (3 planes x 256 lanes), so that a read of a lane's window block -1
-// (left reads near the window start) stays inside the workgroup's LDS.
-constexpr uint32_t kTextTableMin = 3u * 256u;
+// Layouts that the host code (pass.cpp) and the kernels share, each defined
+// once here.
+// the words of a slot's counters (Ctx::Slot::small); kBatchTotals copies all
+// kSlotWords of them into the batch's record
+enum SlotWord : uint32_t {
+    kSwHitCount = 1, kSwFlags = 2, kSwFilled = 3, kSwTaskCount = 4,
+    kSwSeedTasks = 5,  // taskCount once the batch's seed tasks are all written (an early text launch's end)
+    kSwSeedCount = 6, kSlotWords = 8
+};
+// the bits of a flags word (a slot's kSwFlags; the locate chain's own word)
+enum Flag : uint32_t {
+    kFlagStack = 1,      // FM DFS stack bound violated
+    kFlagHits = 2,       // hit buffer too small
+    kFlagLocate = 4,     // locate walked off the SA samples
+    kFlagTasks = 8,      // task buffer too small
+    kFlagTextStack = 16  // text DFS stack bound violated
+};
+// a slot's striped work queues (Ctx::Slot::queues), kQueueWords counter words
+// each (search.hip: kStripes * kStripeStride): the FM phase's seeds, the text
+// phase's seed tasks, the tasks the FM phase appended
+constexpr uint32_t kQueueWords = 256;
+enum QueueAt : uint32_t { kQueueSeeds = 0, kQueueSeedTasks = kQueueWords, kQueueFmTasks = 2 * kQueueWords,
+                         kQueuesWords = 3 * kQueueWords };
+// One batch's record in pinned host memory (Ctx::pinned), written by
+// kBatchTotals (words 0-11), the locate flags' copy (7) and limitBatch (12-13)
+struct BatchRecord {
+    uint32_t slot[7];      // the slot's counters, by SlotWord
+    uint32_t locateFlags;  // the locate chain's flags word (kFlagLocate)
+    uint64_t rows;         // the batch's row total
+    uint32_t nbig, nhuge;  // long / huge segments
+    uint64_t kept;         // rows --max_hits keeps
+    uint32_t pad[2];
+};
+static_assert(sizeof(BatchRecord) == 64 && offsetof(BatchRecord, slot) == 0 &&
+              offsetof(BatchRecord, locateFlags) == 4 * 7 && offsetof(BatchRecord, rows) == 4 * kSlotWords &&
+              offsetof(BatchRecord, nbig) == 4 * 10 && offsetof(BatchRecord, nhuge) == 4 * 11 &&
+              offsetof(BatchRecord, kept) == 4 * 12, "BatchRecord is what kBatchTotals and limitBatch write");
 
-// work counters of count mode (sahara_stats): [0..15] as SearchArgs::counters
-// lists them, [16] text tasks that came with their text position (kTaskPos),
-// [17..19] text-kernel cycles idle / in grab / whole wave lives
+// work counters of count mode (sahara_stats; Ctx::counters)
 constexpr uint32_t kCounters = 56;
+enum Counter : uint32_t {
+    kCtNodes = 0, kCtRankNodes = 1, kCtExtLines = 2, kCtLfSteps = 3, kCtDigest = 4, kCtTextNodes = 5,
+    kCtTextTasks = 6, kCtFmIter = 7, kCtTextIter = 8, kCtTextActive = 9, kCtTextRefills = 10,
+    kCtCyRefill = 11, kCtCyStep = 12, kCtCyEmit = 13,  // text-kernel cycles
+    kCtCompareSteps = 14, kCtTextSteps = 15,
+    kCtPosTasks = 16,  // text tasks that came with their text position (kTaskPos)
+    // TextBatchArgs::probe, the pass's first text launch, wall clock (10 ns):
+    // per wave that saw the queue dry, its time after that and their number
+    kCtDryRun = 30, kCtDryWaves = 31,
+    kCtBornMin = 33, kCtBornMax = 34, kCtEndMax = 35, kCtLifeSum = 36, kCtEndMin = 37,  // wave starts / ends (minima start at ~0)
+    kCtDryMin = 38, kCtDryMax = 39,  // the queue seen dry first / last
+    kCtIterPre = 40, kCtActPre = 41, kCtIterPost = 42, kCtActPost = 43,  // iterations, busy lanes before / after
+    kCtStolen = 45,                                                      // text nodes stolen (all launches)
+    kCtWallPreRefill = 46, kCtWallPreStep = 47, kCtWallPostRefill = 48, kCtWallPostStep = 49
+};
 // a task record whose x is already a text position (a k-mer seed with one
 // occurrence: DeviceIndex::kmerPos), not an SA row: bit 31 of its y (|t|)
 constexpr uint32_t kTaskPos = 0x80000000u;
@@ -118,7 +165,7 @@ struct TextBatchArgs {
                              // lane of their wave (with its window and pattern) once this many are idle (0: off)
     uint32_t* qcnt;          // as SearchArgs: rows ranked where the hits are written (the FM phase's counts)
     uint32_t* rank;
-    uint32_t probe;          // (count mode) wave lives on the wall clock into counters [30..49] ...
+    uint32_t probe;          // (count mode) wave lives on the wall clock into counters kCtDryRun.. ...
     uint32_t isFirst;        // ... for the pass's first launch only
 };
 
@@ -184,9 +231,9 @@ uint32_t scanTiles(uint32_t nq);  // u64 partials querySegments needs
 void querySegments(uint32_t* qcnt, uint32_t nq, uint64_t* qoff, uint64_t* partial, uint32_t* big, uint32_t* nbig,
                    uint32_t* huge, uint32_t* nhuge, hipStream_t st);
 void launchLocate(const LocateArgs& a, bool count, hipStream_t st);
-// a batch's totals into pinned host memory in one launch: out[0..8) = the
-// slot's counters (small), out[8..10) = the row total (u64), out[10..12) =
-// the long / huge segment counts
+// a batch's totals into pinned host memory in one launch: the first 12 words
+// of its BatchRecord (the slot's counters, the row total, the long / huge
+// segment counts)
 void launchBatchTotals(const uint32_t* small, const uint64_t* rowTotal, const uint32_t* segCounts, uint32_t* out,
                        hipStream_t st);
 size_t bigSortTempBytes(uint64_t rows, uint32_t nbig);

@@ -174,6 +174,7 @@ struct SlotRange {
 // device-wide; eight of them keep a chunk grab off the critical path.
 constexpr uint32_t kStripes = 8;
 constexpr uint32_t kStripeStride = 32;  // u32 between counters
+static_assert(kStripes * kStripeStride == kQueueWords, "a striped queue is one region of Ctx::Slot::queues");
 struct StripedQueue {
     uint32_t* ctr;
     uint32_t n, stripe, tries = 0;
@@ -364,7 +365,7 @@ __global__ __launch_bounds__(256) void kSeedItems(SeedArgs a) {
                                              (cur[k].w & 0xFFFFu) | (a.kmerPos ? kTaskPos : 0u), pid,
                                              (cur[k].w & 0x00FFFFFFu) | (sIdx << 24));
                 else
-                    atomicOr(a.flags, 8u);
+                    atomicOr(a.flags, kFlagTasks);
                 ++cTasks;
             }
             slot += (uint32_t)__popcll(m[k]);
@@ -373,8 +374,8 @@ __global__ __launch_bounds__(256) void kSeedItems(SeedArgs a) {
         __syncthreads();  // wcount / blockBase reused next round
     }
     if (a.counters && cTasks) {
-        atomicAdd(a.counters + 6, (unsigned long long)cTasks);
-        if (a.kmerPos) atomicAdd(a.counters + 16, (unsigned long long)cTasks);
+        atomicAdd(a.counters + kCtTextTasks, (unsigned long long)cTasks);
+        if (a.kmerPos) atomicAdd(a.counters + kCtPosTasks, (unsigned long long)cTasks);
     }
 }
 
@@ -545,7 +546,7 @@ __global__ __launch_bounds__(256) void kSearchFM(SearchArgs a) {
                     a.hits[slot] = make_uint4(pid, cur.x, cur.z, (cur.w >> 16) & 0xFu);
                     a.rank[slot] = atomicAdd(a.qcnt + pid, cur.z);  // its first row's place in the query's segment
                 } else {
-                    atomicOr(a.flags, 2u);
+                    atomicOr(a.flags, kFlagHits);
                 }
                 have = false;
                 ++filled;
@@ -561,7 +562,7 @@ __global__ __launch_bounds__(256) void kSearchFM(SearchArgs a) {
                 if (taskSlots.take(want, lane, ltMask, a.taskCount, slot) && want) {
                     if (slot < a.taskCap)
                         a.tasks[slot] = make_uint4(cur.x + j, tlen, pid, (cur.w & 0x00FFFFFFu) | (sIdx << 24));
-                    else atomicOr(a.flags, 8u);
+                    else atomicOr(a.flags, kFlagTasks);
                     if (COUNT) ++cTasks;
                 }
             }
@@ -646,7 +647,7 @@ __global__ __launch_bounds__(256) void kSearchFM(SearchArgs a) {
                     stackPut(sp, v);
                     ++sp;
                 } else {
-                    atomicOr(a.flags, 1u);
+                    atomicOr(a.flags, kFlagStack);
                 }
             };
             const uint4 ins = make_uint4(cur.x, cur.y, cur.z, childMeta(pos, e, lastL, lastR, right, dl, 3));
@@ -659,11 +660,11 @@ __global__ __launch_bounds__(256) void kSearchFM(SearchArgs a) {
     taskSlots.close(lane, a.tasks, a.taskCap);
     if (filled) atomicAdd(a.filled, filled);  // per-lane counts
     if (COUNT) {
-        atomicAdd(a.counters + 0, (unsigned long long)cNodes);
-        atomicAdd(a.counters + 1, (unsigned long long)cRank);
-        atomicAdd(a.counters + 2, (unsigned long long)cLines);
-        atomicAdd(a.counters + 6, (unsigned long long)cTasks);
-        if (cIter) atomicAdd(a.counters + 7, (unsigned long long)cIter);
+        atomicAdd(a.counters + kCtNodes, (unsigned long long)cNodes);
+        atomicAdd(a.counters + kCtRankNodes, (unsigned long long)cRank);
+        atomicAdd(a.counters + kCtExtLines, (unsigned long long)cLines);
+        atomicAdd(a.counters + kCtTextTasks, (unsigned long long)cTasks);
+        if (cIter) atomicAdd(a.counters + kCtFmIter, (unsigned long long)cIter);
     }
 }
 
@@ -1227,7 +1228,7 @@ __global__ __launch_bounds__(256) void kSearchTextBatch(TextBatchArgs a) {
                     rankVal = atomicAdd(a.qcnt + pid, 1u);
                     rankSlot = s;
                 } else {
-                    atomicOr(a.flags, 2u);
+                    atomicOr(a.flags, kFlagHits);
                 }
                 ++filled;
             }
@@ -1241,43 +1242,43 @@ __global__ __launch_bounds__(256) void kSearchTextBatch(TextBatchArgs a) {
     }
     if (kProbe && a.probe && a.isFirst && lane == 0) {
         const uint64_t wEnd = wall_clock64(), w0 = wBorn[threadIdx.x >> 6], wd = wDrain[threadIdx.x >> 6];
-        atomicMin(a.counters + 33, (unsigned long long)w0);
-        atomicMax(a.counters + 34, (unsigned long long)w0);
-        atomicMax(a.counters + 35, (unsigned long long)wEnd);
-        atomicAdd(a.counters + 36, (unsigned long long)(wEnd - w0));
-        atomicMin(a.counters + 37, (unsigned long long)wEnd);
+        atomicMin(a.counters + kCtBornMin, (unsigned long long)w0);
+        atomicMax(a.counters + kCtBornMax, (unsigned long long)w0);
+        atomicMax(a.counters + kCtEndMax, (unsigned long long)wEnd);
+        atomicAdd(a.counters + kCtLifeSum, (unsigned long long)(wEnd - w0));
+        atomicMin(a.counters + kCtEndMin, (unsigned long long)wEnd);
         if (wd) {
-            atomicMin(a.counters + 38, (unsigned long long)wd);
-            atomicMax(a.counters + 39, (unsigned long long)wd);
-            atomicAdd(a.counters + 30, (unsigned long long)(wEnd - wd));
-            atomicAdd(a.counters + 31, 1ull);
+            atomicMin(a.counters + kCtDryMin, (unsigned long long)wd);
+            atomicMax(a.counters + kCtDryMax, (unsigned long long)wd);
+            atomicAdd(a.counters + kCtDryRun, (unsigned long long)(wEnd - wd));
+            atomicAdd(a.counters + kCtDryWaves, 1ull);
         }
-        atomicAdd(a.counters + 40, (unsigned long long)pIterPre);
-        atomicAdd(a.counters + 41, (unsigned long long)pActPre);
-        atomicAdd(a.counters + 42, (unsigned long long)pIterPost);
-        atomicAdd(a.counters + 43, (unsigned long long)pActPost);
-        atomicAdd(a.counters + 46, (unsigned long long)pwPreA);
-        atomicAdd(a.counters + 47, (unsigned long long)pwPreB);
-        atomicAdd(a.counters + 48, (unsigned long long)pwPostA);
-        atomicAdd(a.counters + 49, (unsigned long long)pwPostB);
+        atomicAdd(a.counters + kCtIterPre, (unsigned long long)pIterPre);
+        atomicAdd(a.counters + kCtActPre, (unsigned long long)pActPre);
+        atomicAdd(a.counters + kCtIterPost, (unsigned long long)pIterPost);
+        atomicAdd(a.counters + kCtActPost, (unsigned long long)pActPost);
+        atomicAdd(a.counters + kCtWallPreRefill, (unsigned long long)pwPreA);
+        atomicAdd(a.counters + kCtWallPreStep, (unsigned long long)pwPreB);
+        atomicAdd(a.counters + kCtWallPostRefill, (unsigned long long)pwPostA);
+        atomicAdd(a.counters + kCtWallPostStep, (unsigned long long)pwPostB);
     }
     hitSlots.close(lane, a.hits, a.hitCap);
     if (rankSlot != ~0u) a.rank[rankSlot] = rankVal;
     if (filled) atomicAdd(a.filled, filled);  // per-lane counts
-    if (__any(bad) && lane == 0) atomicOr(a.flags, 16u);
+    if (__any(bad) && lane == 0) atomicOr(a.flags, kFlagTextStack);
     if (COUNT) {
-        atomicAdd(a.counters + 5, (unsigned long long)cNodes);
+        atomicAdd(a.counters + kCtTextNodes, (unsigned long long)cNodes);
         if (lane == 0) {
-            atomicAdd(a.counters + 8, (unsigned long long)tIter);
-            atomicAdd(a.counters + 9, (unsigned long long)tActive);
-            atomicAdd(a.counters + 10, (unsigned long long)tRefill);
-            atomicAdd(a.counters + 11, (unsigned long long)cyRefill);
-            atomicAdd(a.counters + 12, (unsigned long long)cyStep);
-            atomicAdd(a.counters + 13, (unsigned long long)cyEmit);
+            atomicAdd(a.counters + kCtTextIter, (unsigned long long)tIter);
+            atomicAdd(a.counters + kCtTextActive, (unsigned long long)tActive);
+            atomicAdd(a.counters + kCtTextRefills, (unsigned long long)tRefill);
+            atomicAdd(a.counters + kCtCyRefill, (unsigned long long)cyRefill);
+            atomicAdd(a.counters + kCtCyStep, (unsigned long long)cyStep);
+            atomicAdd(a.counters + kCtCyEmit, (unsigned long long)cyEmit);
         }
-        atomicAdd(a.counters + 14, (unsigned long long)cCmp);
-        atomicAdd(a.counters + 15, (unsigned long long)cSteps);
-        if (cSteal) atomicAdd(a.counters + 45, (unsigned long long)cSteal);
+        atomicAdd(a.counters + kCtCompareSteps, (unsigned long long)cCmp);
+        atomicAdd(a.counters + kCtTextSteps, (unsigned long long)cSteps);
+        if (cSteal) atomicAdd(a.counters + kCtStolen, (unsigned long long)cSteal);
     }
 }
 
@@ -1421,7 +1422,7 @@ __global__ __launch_bounds__(256) void kLocate(LocateArgs a) {
                                        (uint64_t)a2.z | ((uint64_t)a2.w << 32)};
                 const uint32_t c = symAt(p, o);
                 if (c == 0 || st >= a.rate) {  // cannot happen on a well-formed index
-                    atomicOr(a.flags, 4u);
+                    atomicOr(a.flags, kFlagLocate);
                     break;
                 }
                 const uint32_t cnt[5] = {a0.x, a0.y, a0.z, a0.w, a1.x};
@@ -2164,7 +2165,7 @@ uint32_t scanTiles(uint32_t nq) { return (nq + 1 + kScanTile - 1) / kScanTile; }
 __global__ void kBatchTotals(const uint32_t* __restrict__ small, const uint64_t* __restrict__ rowTotal,
                              const uint32_t* __restrict__ segCounts, uint32_t* __restrict__ out) {
     const uint32_t i = threadIdx.x;
-    if (i < 8) out[i] = small[i];
+    if (i < kSlotWords) out[i] = small[i];
     else if (i < 10) out[i] = (uint32_t)(*rowTotal >> (32 * (i - 8)));
     else if (i < 12) out[i] = segCounts[i - 10];
 }

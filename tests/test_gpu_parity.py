@@ -544,6 +544,8 @@ def test_fm_phase_work_stealing(gpu_device, monkeypatch, steal):
             counts[at] = (st["nodes"], st["ext_lines"], st["hits"])
             assert np.array_equal(hits_as_rows(gpu.fetch()), want), (mode, split, at)
         assert counts["0"] == counts[steal], (mode, split, counts)
+        if mode[0] and split is None:  # after the FM-only leg the default has text tasks again (knobs are read per pass)
+            assert st["conversions"] > 0, (mode, split, st["conversions"])
     gpu.set_mode(verify=True, locate_sa=True)
     monkeypatch.delenv("SAHARA_SPLIT", raising=False)
     assert np.array_equal(hits_as_rows(sa.search(gpu, pats, scheme)), want)
