@@ -455,7 +455,7 @@ int sahara_gpu_fetch(void* ctx, sahara_hit* out, uint64_t capacity, uint64_t* n_
         Ctx* c = ctxOf(ctx);
         if (n_hits) *n_hits = c->nout;
         if (capacity < c->nout) throw Error("sahara_gpu_fetch: capacity too small");
-        if (c->nout) SH_HIP(hipMemcpy(out, c->out.ptr, c->nout * sizeof(sahara_hit), hipMemcpyDeviceToHost));
+        if (c->nout) SH_HIP(hipMemcpy(out, c->wholeHits(), c->nout * sizeof(sahara_hit), hipMemcpyDeviceToHost));
     });
 }
 
@@ -465,7 +465,7 @@ int sahara_gpu_copy_hits(void* ctx, void* dst_device, uint64_t capacity, uint64_
         if (n_hits) *n_hits = c->nout;
         if (capacity < c->nout) throw Error("sahara_gpu_copy_hits: capacity too small");
         if (c->nout && !dst_device) throw Error("sahara_gpu_copy_hits: null destination");
-        launchCopyHits(c->out.ptr, c->nout, qid_offset, static_cast<sahara_hit*>(dst_device), c->st);
+        launchCopyHits(c->wholeHits(), c->nout, qid_offset, static_cast<sahara_hit*>(dst_device), c->st);
         SH_HIP(hipStreamSynchronize(c->st));
     });
 }
@@ -474,7 +474,7 @@ int sahara_gpu_digest(void* ctx, uint64_t* digest) {
     return guarded([&] {
         Ctx* c = ctxOf(ctx);
         SH_HIP(hipMemsetAsync(c->counters.ptr + 4, 0, 8, c->st));
-        launchDigest(c->out.ptr, c->nout, c->counters.ptr + 4, c->st);
+        launchDigest(c->wholeHits(), c->nout, c->counters.ptr + 4, c->st);
         unsigned long long d = 0;
         SH_HIP(hipMemcpyAsync(&d, c->counters.ptr + 4, 8, hipMemcpyDeviceToHost, c->st));
         SH_HIP(hipStreamSynchronize(c->st));
@@ -764,7 +764,7 @@ static void searchStreamed(Ctx* c, const uint8_t* src, uint64_t rows, bool rc, u
     const auto t0 = std::chrono::steady_clock::now();
     if (hostLimit) {
         std::vector<sahara_hit> v(c->nout);
-        if (c->nout) SH_HIP(hipMemcpy(v.data(), c->out.ptr, c->nout * sizeof(sahara_hit), hipMemcpyDeviceToHost));
+        if (c->nout) SH_HIP(hipMemcpy(v.data(), c->wholeHits(), c->nout * sizeof(sahara_hit), hipMemcpyDeviceToHost));
         limitHits(v, max_hits);
         handOver(v, hits, n_hits);
     } else {
@@ -778,11 +778,12 @@ static void searchStreamed(Ctx* c, const uint8_t* src, uint64_t rows, bool rc, u
         sahara_hit* buf = static_cast<sahara_hit*>(sink.get());
         if (c->nout > c->sk.done) {  // the rest (or all) of the hits
             const size_t bytes = (c->nout - c->sk.done) * sizeof(sahara_hit);
+            const sahara_hit* src = c->wholeHits() + c->sk.done;
             if (pinned) {
-                SH_HIP(hipMemcpyAsync(buf + c->sk.done, c->out.ptr + c->sk.done, bytes, hipMemcpyDeviceToHost, c->st));
+                SH_HIP(hipMemcpyAsync(buf + c->sk.done, src, bytes, hipMemcpyDeviceToHost, c->st));
                 SH_HIP(hipStreamSynchronize(c->st));
             } else {
-                copyOut(c, buf + c->sk.done, c->out.ptr + c->sk.done, bytes);
+                copyOut(c, buf + c->sk.done, src, bytes);
             }
         }
         *hits = static_cast<sahara_hit*>(sink.release());
@@ -844,9 +845,10 @@ static void searchReadsCompact(Ctx* c, const uint8_t* reads, uint64_t n_reads, u
     size_t capBytes = 0;
     recs.reset(allocPinned(sinkEstimate(c, R.npat) * 8, &pinned, &capBytes, true, true));
     if (!recs) throw Error("out of host memory for hits");
+    c->sk.recs = true;
     c->sk.blockRecs = pinned ? static_cast<uint64_t*>(recs.get()) : nullptr;
     c->sk.cap = pinned ? capBytes / 8 : 0;
-    if (c->sk.cap) c->outRecs.reserve(c->sk.cap);
+    if (c->sk.cap) c->reserveRecs(c->sk.cap);
     uint64_t recCap = capBytes / 8;
     passStarted = true;
     run(c, false);
@@ -856,30 +858,26 @@ static void searchReadsCompact(Ctx* c, const uint8_t* reads, uint64_t n_reads, u
     const auto t0 = clk::now();
     if (!c->sk.blockRecs || c->sk.done < c->nout) {
         // the sink held too few (or is not pinned): the records of every
-        // batch again, from the device-resident hits, into one that fits
+        // batch again, from the device-resident records (c->outRecs holds the
+        // whole call's: pass.cpp finish), into one that fits
         if (c->nout > recCap) {
             recs.reset();
             recs.reset(allocPinned(c->nout * 8, &pinned, &capBytes, true, true));
             if (!recs) throw Error("out of host memory for hits");
             recCap = capBytes / 8;
         }
-        uint64_t* dst = static_cast<uint64_t*>(recs.get());
-        if (!pinned) {
-            c->outC.reserve(std::max<uint64_t>(c->nout, 1));
-            dst = c->outC.ptr;
-        }
         uint64_t b0 = 0;
-        for (size_t b = 0; b < c->batchQ0.size(); ++b) {
-            launchCompactHits(c->out.ptr + b0, c->batchEnd[b] - b0, c->batchQ0[b], c->I.dRecStarts.ptr, dst + b0,
-                              c->st, pinned ? 256u : 8192u);
-            b0 = c->batchEnd[b];
-        }
-        if (!pinned && c->nout) SH_HIP(hipMemcpyAsync(recs.get(), dst, c->nout * 8, hipMemcpyDeviceToHost, c->st));
+        for (size_t b = 0; b < c->batchQ0.size(); b0 = c->batchEnd[b], ++b)
+            if (!c->batchDirect[b])  // (a batch of 2^28 queries or more: whole hits in c->out)
+                launchCompactHits(c->out.ptr + b0, c->batchEnd[b] - b0, c->batchQ0[b], c->I.dRecStarts.ptr,
+                                  c->outRecs.ptr + b0, c->st);
+        if (c->nout) SH_HIP(hipMemcpyAsync(recs.get(), c->outRecs.ptr, c->nout * 8, hipMemcpyDeviceToHost, c->st));
         SH_HIP(hipStreamSynchronize(c->st));
     }
     c->stats.output_ms = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
     failed.dismiss();
     c->sk.blockRecs = nullptr;
+    c->sk.recs = false;
     c->sk.streaming = false;
     c->stats.stage_ms = c->up.hostMs;
     for (int b = 0; b < 3; ++b) c->stats.upload_chunks[b] = c->up.chunks[b];
@@ -971,7 +969,7 @@ int sahara_gpu_prepare(void* ctx, uint64_t n_patterns, uint32_t len) {
             freeHits(p);
         }
         if (!c) return;  // (NULL context: the host part only, e.g. beside the index load)
-        if (pinned) c->outRecs.reserve(capBytes / 8);
+        if (pinned) c->reserveRecs(capBytes / 8);
         c->out.reserve(est);
         // the slots and the locate chain's buffers of a streamed pass, from
         // the pass's own sizing (pass.cpp; the keys sized for a batch's rows

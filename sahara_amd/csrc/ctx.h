@@ -271,6 +271,7 @@ struct Ctx {
         bool compact = false, pinned = false;
         uint64_t downJobs = 0;            // batches handed to the expander this call
         uint64_t* blockRecs = nullptr;    // sahara_gpu_search_reads_compact's sink (below)
+        bool recs = false;                // ... its call: compact records are what it returns (sink pinned or not)
         // --max_hits n applied per batch on the device (single-part indexes;
         // limitBatch), 0: off
         uint32_t limitN = 0;
@@ -283,15 +284,30 @@ struct Ctx {
     DevBuf<uint64_t> outC;
     static constexpr size_t kDownSlots = 3, kDownSlot = 64u << 20;  // 8M records per batch
     std::unique_ptr<Expander> expander;
-    // sahara_gpu_search_reads_compact: each batch's hits as 8-B records,
-    // made by kCompactHits in HBM (outRecs, sk.cap entries) and copied by a
+    // sahara_gpu_search_reads_compact: each batch's hits as 8-B records in
+    // HBM (outRecs, at the batch's place among the call's hits) and copied by a
     // copy engine on stF into the pinned host buffer sk.blockRecs (sk.cap records); per
     // batch its first qid and one past its last record (the blocks of
     // sahara_hit_blocks). (Written by the kernel straight into the sink over
     // PCIe, the records held CU slots beside the text phase: C3 592M against
     // 632M reads/s with the copy engine, profiles/r03_pcie_compact_dma.txt.)
+    // A batch whose sink takes compact records is sorted straight into them
+    // (pass.cpp finish: batchDirect), and `out` holds nothing of it until a
+    // reader of the whole hits asks (wholeHits below); the Expander's
+    // batches go through outRecs in the same way.
     DevBuf<uint64_t> outRecs;
     std::vector<uint64_t> batchQ0, batchEnd;
+    std::vector<uint8_t> batchDirect;     // per batch: its hits are in outRecs only
+    bool outStale = false;                // some batch is: `out` lacks its hits
+    // The last pass's hits as whole records, device-resident: `out`, after
+    // the batches that were sorted into compact records are expanded into it
+    // (once, off any timed path: sahara_gpu_fetch, _digest, _copy_hits and the
+    // copy-out of a sink that was too small).
+    const sahara_hit* wholeHits();
+    void reserveRecs(size_t n) {          // (outRecs may be all there is of the last call's hits)
+        if (n > outRecs.cap) wholeHits();
+        outRecs.reserve(n);
+    }
     std::vector<uint64_t> recStartsEnd;   // record starts + the text length (sahara_hit_blocks.rec_starts)
     DevBuf<uint32_t> limitCnt;            // limitBatch's buffers (sk.limitN)
     DevBuf<uint64_t> limitOff;

@@ -91,6 +91,20 @@ void runOne(Ctx* c, bool count) {
     c->stats = S;
 }
 
+const sahara_hit* Ctx::wholeHits() {
+    if (outStale) {  // (the pass is over: its streams are synchronised)
+        if (out.cap < nout) out.growKeeping(nout, out.cap, st);  // other batches' hits are in it already
+        uint64_t b0 = 0;
+        for (size_t b = 0; b < batchEnd.size(); b0 = batchEnd[b], ++b)
+            if (batchDirect[b])
+                launchExpandRecs(outRecs.ptr + b0, batchEnd[b] - b0, batchQ0[b], I.dRecStarts.ptr,
+                                 (uint32_t)I.recStarts.size(), out.ptr + b0, st);
+        SH_HIP(hipStreamSynchronize(st));
+        outStale = false;
+    }
+    return out.ptr;
+}
+
 void initWorkCaps(Ctx* c, uint64_t maxBatch, const PassKnobs& k) {
     if (c->hitCap == 0) c->hitCap = k.hitCap ? k.hitCap : firstWorkCap(maxBatch);
     if (c->taskCap == 0) c->taskCap = k.taskCap ? k.taskCap : firstWorkCap(maxBatch);
@@ -339,12 +353,14 @@ struct Pass {
     Ctx::Slot& slotOf(uint64_t b) const { return c->slot[b % Ctx::kSlots]; }
 
     // a slot's counters and queues are zero when its `free` event fires:
-    // at the pass's start for the first use, after its locate (finish) for the next
+    // at the pass's start for the first use (resetSlot), after its locate
+    // for the next (finish: kBatchTotals has cleared them, freeSlot)
     void resetSlot(Ctx::Slot& sl, hipStream_t s) {
         SH_HIP(hipMemsetAsync(sl.small.ptr, 0, kSlotWords * sizeof(uint32_t), s));
         SH_HIP(hipMemsetAsync(sl.queues.ptr, 0, kQueuesWords * sizeof(uint32_t), s));
         SH_HIP(hipEventRecord(sl.free, s));
     }
+    void freeSlot(Ctx::Slot& sl, hipStream_t s) { SH_HIP(hipEventRecord(sl.free, s)); }
 
     // the batch's seed tasks are all written (stream sD): the first batch's
     // text phase launches on them (the count snapshot in kSwSeedTasks) before
@@ -470,7 +486,8 @@ struct Pass {
     }
 
     // locate: row offsets (exclusive scan of len), SA / LF locate, canonical
-    // sort, decode into the device-resident output, on stream sC. Needs the
+    // sort into the device-resident output (whole hits, or compact records
+    // where the call's sink takes those), on stream sC. Needs the
     // batch's counts (host waits for its text phase). Returns false on
     // overflow; `finishCheck` then reads the locate flags and timings.
     bool finish(uint64_t b) {
@@ -487,13 +504,14 @@ struct Pass {
         // anyway, so its scan is wasted work, not wrong work.
         SH_HIP(hipStreamWaitEvent(sC, sl.textDone, 0));
         SH_HIP(hipEventRecord(c->locStart, sC));
-        SH_HIP(hipMemsetAsync(c->small.ptr, 0, 8 * sizeof(uint32_t), sC));
+        // (the chain's words of c->small are zero here: cleared at the pass's
+        // start, and by kBatchTotals and kLocateFlagsOut once read)
         c->partial.reserve(scanTiles((uint32_t)nb));
         uint32_t* const segCounts = c->small.ptr + kLocSegCounts;
         querySegments(sl.qcnt.ptr, (uint32_t)nb, c->qoff.ptr, c->partial.ptr, c->big.ptr, segCounts, c->huge.ptr,
                       segCounts + 1, sC);
         BatchRecord& rec = c->pinned.ptr[b];
-        launchBatchTotals(sl.small.ptr, c->qoff.ptr + nb, segCounts, rec.slot, sC);
+        launchBatchTotals(sl.small.ptr, sl.queues.ptr, c->qoff.ptr + nb, segCounts, rec.slot, sC);
         SH_HIP(hipEventRecord(P.sleepy ? c->totalsDownSleep : c->totalsDown, sC));
         if (P.sleepy) waitSleepy(c->totalsDownSleep, P.k.pollUs);
         else SH_HIP(hipEventSynchronize(c->totalsDown));
@@ -507,8 +525,8 @@ struct Pass {
             // thread; they grow after the pass, before the serial re-run)
             if (flags & kFlagTasks) growCap(P.serial ? c->taskCap : seenTask, rec.slot[kSwTaskCount]);
             if (flags & kFlagHits) growCap(P.serial ? c->hitCap : seenHit, rec.slot[kSwHitCount]);
-            overflow = true;  // (the scan zeroed the slot's per-query counts)
-            resetSlot(sl, sC);
+            overflow = true;  // (the scan zeroed the slot's per-query counts, kBatchTotals its counters)
+            freeSlot(sl, sC);
             return false;
         }
         // reserved slots incl. len-0 holes; a wave's last range may reach past
@@ -522,23 +540,41 @@ struct Pass {
         if (nhuge) c->k1.reserve(std::max<uint64_t>(rows, 1));
         launchLocate(locateArgs(c, sl, nh), P.count, sC);
         SH_HIP(hipEventRecord(c->locDone, sC));
-        resetSlot(sl, sC);  // the slot's hits are consumed
+        freeSlot(sl, sC);  // the slot's hits are consumed
         if (nhuge) c->tmp.reserve(bigSortTempBytes(rows, nhuge) + 256);
-        if (c->nout + rows > c->out.cap) {  // grow the device-resident output
+        // A batch whose sink takes compact records is sorted straight into
+        // them: the record is the sort key with the batch-local query in
+        // front, so nothing is decoded and nothing of the batch goes into
+        // c->out (Ctx::wholeHits expands it should a reader of c->out ask).
+        const uint64_t end = c->nout + rows;
+        const bool toExpander = !c->sk.blockRecs && c->sk.ok && end <= c->sk.cap && c->sk.compact &&
+                                rows * sizeof(uint64_t) <= Ctx::kDownSlot;
+        const bool direct = (c->sk.recs || toExpander) && c->sk.limitN == 0 && c->more.empty() && nb < (1ull << 28);
+        auto growFor = [&](auto& buf) {  // a device-resident output of the call, kept as it grows
+            if (end <= buf.cap) return;
             SH_HIP(hipStreamSynchronize(c->stF));  // sink copies may still read the old buffer
-            c->out.growKeeping(std::max<size_t>((c->nout + rows) + (c->nout + rows) / 2, 1024), c->nout, sC);
+            buf.growKeeping(std::max<size_t>(end + end / 2, 1024), std::min<size_t>(c->nout, buf.cap), sC);
+        };
+        if (direct || c->sk.recs) growFor(c->outRecs);
+        if (direct) {
+            sortCompact(c->k0.ptr, c->k1.ptr, rows, c->qoff.ptr, (uint32_t)nb, c->big.ptr, nbig, c->huge.ptr, nhuge,
+                        c->outRecs.ptr + c->nout, c->tmp.ptr, c->tmp.cap, sC);
+            if (rows) c->outStale = true;
+        } else {
+            growFor(c->out);
+            sortDecode(c->k0.ptr, c->k1.ptr, rows, c->qoff.ptr, (uint32_t)nb, c->big.ptr, nbig, c->huge.ptr, nhuge, q0,
+                       c->I.dRecStarts.ptr, (uint32_t)c->I.recStarts.size(), c->out.ptr + c->nout, c->tmp.ptr,
+                       c->tmp.cap, sC);
         }
-        sortDecode(c->k0.ptr, c->k1.ptr, rows, c->qoff.ptr, (uint32_t)nb, c->big.ptr, nbig, c->huge.ptr, nhuge, q0,
-                   c->I.dRecStarts.ptr, (uint32_t)c->I.recStarts.size(), c->out.ptr + c->nout, c->tmp.ptr, c->tmp.cap,
-                   sC);
         if (c->sk.limitN)  // --max_hits: this batch's queries keep their n best positions (search_n)
             rows = limitBatch(c->out.ptr + c->nout, rows, c->qoff.ptr, (uint32_t)nb, c->sk.limitN, c->limitCnt,
                               c->limitOff, c->limitBuf, c->tmp, &rec.kept, sC);
         SH_HIP(hipEventRecord(c->sortDone, sC));
         c->batchQ0.push_back(q0);
         c->batchEnd.push_back(c->nout + rows);
-        sinkBatch(q0, nb, rows);
-        SH_HIP(hipMemcpyAsync(&rec.locateFlags, c->small.ptr + kLocFlags, 4, hipMemcpyDeviceToHost, sC));
+        c->batchDirect.push_back(direct && rows ? 1 : 0);
+        sinkBatch(q0, nb, rows, direct);
+        launchLocateFlagsOut(c->small.ptr + kLocFlags, &rec.locateFlags, sC);
         SH_HIP(hipEventRecord(c->flagsDown, sC));
         if (P.sleepy) SH_HIP(hipEventRecord(c->flagsDownSleep, sC));
         c->nout += rows;
@@ -550,19 +586,22 @@ struct Pass {
     // go to host memory on stF while later batches search, while they fit
     // the sink: as compact records into blockRecs, compact through the
     // Expander, whole into a pinned sink, or not at all (the rest of the call's
-    // hits then go after the pass)
-    void sinkBatch(uint64_t q0, uint64_t nb, uint64_t rows) {
+    // hits then go after the pass). direct: the sort has written the batch's
+    // compact records into c->outRecs (finish); else kCompactHits makes them
+    // from the whole hits in c->out.
+    void sinkBatch(uint64_t q0, uint64_t nb, uint64_t rows, bool direct) {
         if (!c->sk.ok || c->nout + rows > c->sk.cap) {
             c->sk.ok = false;
             return;
         }
         const bool compact = c->sk.compact && rows * sizeof(uint64_t) <= Ctx::kDownSlot && nb < (1ull << 28);
         if (rows && c->sk.blockRecs) {
-            // compact records made in HBM on sC (full grid, ~20 us), then
-            // one D2H copy on stF: a copy engine moves them, no workgroup
-            // waits on PCIe writes beside the text phase
-            launchCompactHits(c->out.ptr + c->nout, rows, q0, c->I.dRecStarts.ptr, c->outRecs.ptr + c->nout, sC,
-                              1u << 16);
+            // compact records in HBM on sC (by the sort, or from the whole
+            // hits: full grid, ~20 us), then one D2H copy on stF: a copy engine
+            // moves them, no workgroup waits on PCIe writes beside the text phase
+            if (!direct)
+                launchCompactHits(c->out.ptr + c->nout, rows, q0, c->I.dRecStarts.ptr, c->outRecs.ptr + c->nout, sC,
+                                  1u << 16);
             SH_HIP(hipEventRecord(c->recsMade, sC));
             SH_HIP(hipStreamWaitEvent(c->stF, c->recsMade, 0));
             SH_HIP(hipMemcpyAsync(c->sk.blockRecs + c->nout, c->outRecs.ptr + c->nout, rows * sizeof(uint64_t),
@@ -573,9 +612,12 @@ struct Pass {
             if (j >= Ctx::kDownSlots) c->expander->waitFor(j + 1 - Ctx::kDownSlots);  // the slot is read
             while (c->downEv.size() < Ctx::kDownSlots) c->downEv.emplace_back(hipEventDisableTiming);
             uint64_t* stage = c->downRing.ptr + slot * (Ctx::kDownSlot / sizeof(uint64_t));
-            c->outC.reserve(Ctx::kDownSlots * (Ctx::kDownSlot / sizeof(uint64_t)));
-            uint64_t* dev = c->outC.ptr + slot * (Ctx::kDownSlot / sizeof(uint64_t));
-            launchCompactHits(c->out.ptr + c->nout, rows, q0, c->I.dRecStarts.ptr, dev, sC);
+            uint64_t* dev = c->outRecs.ptr + c->nout;
+            if (!direct) {
+                c->outC.reserve(Ctx::kDownSlots * (Ctx::kDownSlot / sizeof(uint64_t)));
+                dev = c->outC.ptr + slot * (Ctx::kDownSlot / sizeof(uint64_t));
+                launchCompactHits(c->out.ptr + c->nout, rows, q0, c->I.dRecStarts.ptr, dev, sC);
+            }
             SH_HIP(hipEventRecord(c->recsMade, sC));
             SH_HIP(hipStreamWaitEvent(c->stF, c->recsMade, 0));
             SH_HIP(hipMemcpyAsync(stage, dev, rows * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stF));
@@ -696,6 +738,9 @@ void runPass(Ctx* c, bool count, bool redo, sahara_stats& S, bool& overflow) {
     c->sk.ok = c->sk.sink != nullptr || c->sk.blockRecs != nullptr;
     c->batchQ0.clear();
     c->batchEnd.clear();
+    c->batchDirect.clear();
+    c->outStale = false;
+    SH_HIP(hipMemsetAsync(c->small.ptr, 0, 8 * sizeof(uint32_t), ps.sC));  // the locate chain's words (finish)
     for (auto& sl : c->slot) ps.resetSlot(sl, ps.sA);
 
     if (!P.serial) {

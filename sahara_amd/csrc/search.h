@@ -97,7 +97,7 @@ constexpr uint32_t kQueueWords = 256;
 enum QueueAt : uint32_t { kQueueSeeds = 0, kQueueSeedTasks = kQueueWords, kQueueFmTasks = 2 * kQueueWords,
                          kQueuesWords = 3 * kQueueWords };
 // One batch's record in pinned host memory (Ctx::pinned), written by
-// kBatchTotals (words 0-11), the locate flags' copy (7) and limitBatch (12-13)
+// kBatchTotals (words 0-11), kLocateFlagsOut (7) and limitBatch (12-13)
 struct BatchRecord {
     uint32_t slot[7];      // the slot's counters, by SlotWord
     uint32_t locateFlags;  // the locate chain's flags word (kFlagLocate)
@@ -233,15 +233,27 @@ void querySegments(uint32_t* qcnt, uint32_t nq, uint64_t* qoff, uint64_t* partia
 void launchLocate(const LocateArgs& a, bool count, hipStream_t st);
 // a batch's totals into pinned host memory in one launch: the first 12 words
 // of its BatchRecord (the slot's counters, the row total, the long / huge
-// segment counts)
-void launchBatchTotals(const uint32_t* small, const uint64_t* rowTotal, const uint32_t* segCounts, uint32_t* out,
+// segment counts), and the slot reset: small, queues (the slot's counters and
+// queue words) and segCounts are zero afterwards
+void launchBatchTotals(uint32_t* small, uint32_t* queues, const uint64_t* rowTotal, uint32_t* segCounts, uint32_t* out,
                        hipStream_t st);
+// the locate chain's flags word into pinned host memory (BatchRecord::locateFlags); zero afterwards
+void launchLocateFlagsOut(uint32_t* flags, uint32_t* out, hipStream_t st);
 size_t bigSortTempBytes(uint64_t rows, uint32_t nbig);
 // long segments (> 64 rows, listed in big) are sorted in LDS, huge ones
 // (> 2048, listed in huge) by the segmented radix sort
 void sortDecode(uint64_t* k0, uint64_t* k1, uint64_t rows, const uint64_t* qoff, uint32_t nq, const uint32_t* big,
                 uint32_t nbig, const uint32_t* huge, uint32_t nhuge, uint64_t qidBase, const uint64_t* starts,
                 uint32_t nrec, sahara_hit* out, void* tmp, size_t tmpBytes, hipStream_t st);
+// the same sort with the hits written as compact records (launchCompactHits'
+// form, qid relative to the batch): the sorted keys with the batch-local
+// query in front, so no record starts are needed; nq < 2^28
+void sortCompact(uint64_t* k0, uint64_t* k1, uint64_t rows, const uint64_t* qoff, uint32_t nq, const uint32_t* big,
+                 uint32_t nbig, const uint32_t* huge, uint32_t nhuge, uint64_t* out, void* tmp, size_t tmpBytes,
+                 hipStream_t st);
+// compact records of one batch (first qid qidBase) back into whole hits
+void launchExpandRecs(const uint64_t* recs, uint64_t n, uint64_t qidBase, const uint64_t* starts, uint32_t nrec,
+                      sahara_hit* out, hipStream_t st);
 void launchPackPatterns3(const uint8_t* src, uint64_t npat, uint32_t m, uint32_t patBlocks, uint4* dst,
                          hipStream_t st);
 void launchDigest(const sahara_hit* h, uint64_t n, unsigned long long* out, hipStream_t st);

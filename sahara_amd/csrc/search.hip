@@ -48,6 +48,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstring>
+#include <type_traits>
 
 #include <rocprim/rocprim.hpp>
 
@@ -1436,6 +1437,15 @@ __global__ __launch_bounds__(256) void kLocate(LocateArgs a) {
     if (COUNT && steps) atomicAdd(a.counters, (unsigned long long)steps);
 }
 
+// What the sort kernels write per sorted key: the whole 24-B hit, or (COMPACT)
+// the 8-B download record, batch-local query << 36 | key (text position << 4 | e).
+template <bool COMPACT>
+using SortOut = std::conditional_t<COMPACT, uint64_t, sahara_hit>;
+
+__device__ __forceinline__ uint64_t compactRecord(uint64_t k, uint32_t localQuery) {
+    return ((uint64_t)localQuery << 36) | k;
+}
+
 __device__ __forceinline__ sahara_hit decodeKey(uint64_t k, uint64_t qid, const uint64_t* __restrict__ starts,
                                                 uint32_t nrec) {
     const uint64_t gpos = k >> 4;
@@ -1472,16 +1482,20 @@ constexpr uint32_t kTileKeys = 1024;
 constexpr uint32_t kLdsStarts = 256;
 constexpr uint16_t kSkipRow = 0xFFFFu;
 
+// COMPACT: the hits leave as sahara_gpu_search's 8-B download records instead
+// (kCompactHits' form: batch-local query << 36 | key), which is the sorted key
+// with the query in front: no decode, and no record starts are read or staged.
+template <bool COMPACT>
 __global__ __launch_bounds__(256) void kSortDecode(const uint64_t* __restrict__ keys,
                                                   const uint64_t* __restrict__ qoff, uint32_t nq, uint64_t qidBase,
                                                   const uint64_t* __restrict__ starts, uint32_t nrec,
-                                                  sahara_hit* __restrict__ out) {
+                                                  SortOut<COMPACT>* __restrict__ out) {
     __shared__ uint64_t sk[kTileKeys];
     __shared__ uint64_t soff[257];
-    __shared__ uint64_t sst[kLdsStarts];
+    __shared__ uint64_t sst[COMPACT ? 1 : kLdsStarts];
     __shared__ uint16_t sq[kTileKeys];
     const uint32_t t = threadIdx.x, lane = t & 63u;
-    const bool ldsStarts = nrec <= kLdsStarts;
+    const bool ldsStarts = !COMPACT && nrec <= kLdsStarts;
     if (ldsStarts)
         for (uint32_t i = t; i < nrec; i += 256) sst[i] = starts[i];
     auto decode = [&](uint64_t k, uint64_t qid) {
@@ -1507,6 +1521,11 @@ __global__ __launch_bounds__(256) void kSortDecode(const uint64_t* __restrict__ 
         h.err = (uint32_t)(k & 15u);
         h.pos = gpos - s0;
         return h;
+    };
+    // sorted key k of the batch's query lq -> out[i]
+    auto put = [&](uint64_t i, uint64_t k, uint32_t lq) {
+        if constexpr (COMPACT) out[i] = compactRecord(k, lq);
+        else out[i] = decode(k, qidBase + lq);
     };
     for (uint32_t q0 = blockIdx.x * 256u; q0 < nq; q0 += gridDim.x * 256u) {
         const uint32_t q = q0 + t;
@@ -1562,7 +1581,7 @@ __global__ __launch_bounds__(256) void kSortDecode(const uint64_t* __restrict__ 
             __syncthreads();
             for (uint32_t i = t; i < (uint32_t)R; i += 256) {
                 const uint32_t lq = sq[i];
-                if (lq != kSkipRow) out[base + i] = decode(sk[i], qidBase + q0 + lq);
+                if (lq != kSkipRow) put(base + i, sk[i], q0 + lq);
             }
             __syncthreads();  // soff, sk, sq are reused by the next range
             continue;
@@ -1581,7 +1600,7 @@ __global__ __launch_bounds__(256) void kSortDecode(const uint64_t* __restrict__ 
             }
 #pragma unroll
             for (uint32_t i = 0; i < kSmallSeg; ++i)
-                if (i < n) out[b + i] = decode(v[i], qidBase + q);
+                if (i < n) put(b + i, v[i], q);
         }
         uint64_t med = __ballot(n > kSmallSeg && n <= kMediumSeg);
         while (med) {
@@ -1599,20 +1618,24 @@ __global__ __launch_bounds__(256) void kSortDecode(const uint64_t* __restrict__ 
                     v = keepMin ? (v < o ? v : o) : (v < o ? o : v);
                 }
             }
-            if (lane < sn) out[sb + lane] = decode(v, qidBase + sqid);
+            if (lane < sn) put(sb + lane, v, sqid);
         }
     }
 }
 
 // One workgroup per long segment (already sorted): decode.
+template <bool COMPACT>
 __global__ __launch_bounds__(256) void kDecodeBig(const uint64_t* __restrict__ keys, const uint64_t* __restrict__ qoff,
                                                  const uint32_t* __restrict__ big, uint32_t nbig, uint64_t qidBase,
                                                  const uint64_t* __restrict__ starts, uint32_t nrec,
-                                                 sahara_hit* __restrict__ out) {
+                                                 SortOut<COMPACT>* __restrict__ out) {
     for (uint32_t s = blockIdx.x; s < nbig; s += gridDim.x) {
         const uint32_t q = big[s];
         const uint64_t b = qoff[q], e = qoff[q + 1];
-        for (uint64_t i = b + threadIdx.x; i < e; i += blockDim.x) out[i] = decodeKey(keys[i], qidBase + q, starts, nrec);
+        for (uint64_t i = b + threadIdx.x; i < e; i += blockDim.x) {
+            if constexpr (COMPACT) out[i] = compactRecord(keys[i], q);
+            else out[i] = decodeKey(keys[i], qidBase + q, starts, nrec);
+        }
     }
 }
 
@@ -1622,10 +1645,11 @@ __global__ __launch_bounds__(256) void kDecodeBig(const uint64_t* __restrict__ k
 // text phase's workgroups, where rocPRIM's segmented radix sort (whose blocks
 // need more LDS than the text phase leaves free) waited for the text launch
 // to drain, up to 1.3 ms per batch at C3 (profiles/r03_v5_c3_timeline.txt).
+template <bool COMPACT>
 __global__ __launch_bounds__(256) void kSortBigLds(const uint64_t* __restrict__ keys, const uint64_t* __restrict__ qoff,
                                                   const uint32_t* __restrict__ big, uint32_t nbig, uint64_t qidBase,
                                                   const uint64_t* __restrict__ starts, uint32_t nrec,
-                                                  sahara_hit* __restrict__ out) {
+                                                  SortOut<COMPACT>* __restrict__ out) {
     __shared__ uint64_t K[kLdsSeg];
     for (uint32_t s = blockIdx.x; s < nbig; s += gridDim.x) {
         const uint32_t q = big[s];
@@ -1651,7 +1675,10 @@ __global__ __launch_bounds__(256) void kSortBigLds(const uint64_t* __restrict__ 
                 }
                 __syncthreads();
             }
-        for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) out[b + i] = decodeKey(K[i], qidBase + q, starts, nrec);
+        for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
+            if constexpr (COMPACT) out[b + i] = compactRecord(K[i], q);
+            else out[b + i] = decodeKey(K[i], qidBase + q, starts, nrec);
+        }
         __syncthreads();
     }
 }
@@ -2017,6 +2044,33 @@ __global__ void kCompactHits(const sahara_hit* __restrict__ h, uint64_t n, uint6
     }
 }
 
+// The way back, for a batch that the sort wrote as compact records only:
+// record i -> whole hit i (qid = qidBase + its batch-local query). Record
+// starts in LDS for texts of <= kLdsStarts records, as in kSortDecode.
+__global__ __launch_bounds__(256) void kExpandRecs(const uint64_t* __restrict__ recs, uint64_t n, uint64_t qidBase,
+                                                  const uint64_t* __restrict__ starts, uint32_t nrec,
+                                                  sahara_hit* __restrict__ out) {
+    __shared__ uint64_t sst[kLdsStarts];
+    const bool ldsStarts = nrec <= kLdsStarts;  // block-uniform
+    if (ldsStarts) {
+        for (uint32_t i = threadIdx.x; i < nrec; i += blockDim.x) sst[i] = starts[i];
+        __syncthreads();
+    }
+    const uint64_t* const st = ldsStarts ? sst : starts;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t v = recs[i];
+        out[i] = decodeKey(v & ((1ull << 36) - 1), qidBase + (v >> 36), st, nrec);
+    }
+}
+
+void launchExpandRecs(const uint64_t* recs, uint64_t n, uint64_t qidBase, const uint64_t* starts, uint32_t nrec,
+                      sahara_hit* out, hipStream_t st) {
+    if (n == 0) return;
+    const uint64_t blocks = std::min<uint64_t>((n + 255) / 256, 8192);
+    hipLaunchKernelGGL(kExpandRecs, dim3((unsigned)blocks), dim3(256), 0, st, recs, n, qidBase, starts, nrec, out);
+    SH_HIP(hipGetLastError());
+}
+
 // `out` may be page-locked host memory: then the kernel's stores are the
 // PCIe transfer (posted writes, ~link rate), and a few workgroups (maxBlocks)
 // keep it off most CUs.
@@ -2162,17 +2216,40 @@ void querySegments(uint32_t* qcnt, uint32_t nq, uint64_t* qoff, uint64_t* partia
 
 uint32_t scanTiles(uint32_t nq) { return (nq + 1 + kScanTile - 1) / kScanTile; }
 
-__global__ void kBatchTotals(const uint32_t* __restrict__ small, const uint64_t* __restrict__ rowTotal,
-                             const uint32_t* __restrict__ segCounts, uint32_t* __restrict__ out) {
+// ... and clears what it has read, with the slot's queue counters: nothing on
+// the device reads them again before the slot's next batch, so the slot is
+// reset here and not by fills of its own further down the chain.
+__global__ void kBatchTotals(uint32_t* __restrict__ small, uint32_t* __restrict__ queues,
+                             const uint64_t* __restrict__ rowTotal, uint32_t* __restrict__ segCounts,
+                             uint32_t* __restrict__ out) {
     const uint32_t i = threadIdx.x;
-    if (i < kSlotWords) out[i] = small[i];
-    else if (i < 10) out[i] = (uint32_t)(*rowTotal >> (32 * (i - 8)));
-    else if (i < 12) out[i] = segCounts[i - 10];
+    if (i < kSlotWords) {
+        out[i] = small[i];
+        small[i] = 0;
+    } else if (i < 10) {
+        out[i] = (uint32_t)(*rowTotal >> (32 * (i - 8)));
+    } else if (i < 12) {
+        out[i] = segCounts[i - 10];
+        segCounts[i - 10] = 0;
+    }
+    for (uint32_t w = i; w < kQueuesWords; w += blockDim.x) queues[w] = 0;
 }
 
-void launchBatchTotals(const uint32_t* small, const uint64_t* rowTotal, const uint32_t* segCounts, uint32_t* out,
+void launchBatchTotals(uint32_t* small, uint32_t* queues, const uint64_t* rowTotal, uint32_t* segCounts, uint32_t* out,
                        hipStream_t st) {
-    hipLaunchKernelGGL(kBatchTotals, dim3(1), dim3(64), 0, st, small, rowTotal, segCounts, out);
+    hipLaunchKernelGGL(kBatchTotals, dim3(1), dim3(64), 0, st, small, queues, rowTotal, segCounts, out);
+    SH_HIP(hipGetLastError());
+}
+
+// The locate chain's flags word into the batch's record in pinned host memory,
+// cleared for the next batch's chain.
+__global__ void kLocateFlagsOut(uint32_t* __restrict__ flags, uint32_t* __restrict__ out) {
+    *out = *flags;
+    *flags = 0;
+}
+
+void launchLocateFlagsOut(uint32_t* flags, uint32_t* out, hipStream_t st) {
+    hipLaunchKernelGGL(kLocateFlagsOut, dim3(1), dim3(1), 0, st, flags, out);
     SH_HIP(hipGetLastError());
 }
 
@@ -2193,16 +2270,17 @@ size_t bigSortTempBytes(uint64_t rows, uint32_t nbig) {
     return tb;
 }
 
-void sortDecode(uint64_t* k0, uint64_t* k1, uint64_t rows, const uint64_t* qoff, uint32_t nq, const uint32_t* big,
-                uint32_t nbig, const uint32_t* huge, uint32_t nhuge, uint64_t qidBase, const uint64_t* starts,
-                uint32_t nrec, sahara_hit* out, void* tmp, size_t tmpBytes, hipStream_t st) {
+template <bool COMPACT>
+static void sortInto(uint64_t* k0, uint64_t* k1, uint64_t rows, const uint64_t* qoff, uint32_t nq, const uint32_t* big,
+                     uint32_t nbig, const uint32_t* huge, uint32_t nhuge, uint64_t qidBase, const uint64_t* starts,
+                     uint32_t nrec, SortOut<COMPACT>* out, void* tmp, size_t tmpBytes, hipStream_t st) {
     if (rows == 0) return;
     const uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>((nq + 255) / 256, 65536));
-    hipLaunchKernelGGL(kSortDecode, dim3(blocks), dim3(256), 0, st, k0, qoff, nq, qidBase, starts, nrec, out);
+    hipLaunchKernelGGL(kSortDecode<COMPACT>, dim3(blocks), dim3(256), 0, st, k0, qoff, nq, qidBase, starts, nrec, out);
     SH_HIP(hipGetLastError());
     if (nbig) {  // long segments in LDS; huge ones skipped there
-        hipLaunchKernelGGL(kSortBigLds, dim3(std::min<uint32_t>(nbig, 4096)), dim3(256), 0, st, k0, qoff, big, nbig,
-                           qidBase, starts, nrec, out);
+        hipLaunchKernelGGL(kSortBigLds<COMPACT>, dim3(std::min<uint32_t>(nbig, 4096)), dim3(256), 0, st, k0, qoff, big,
+                           nbig, qidBase, starts, nrec, out);
         SH_HIP(hipGetLastError());
     }
     if (nhuge == 0) return;
@@ -2211,9 +2289,21 @@ void sortDecode(uint64_t* k0, uint64_t* k1, uint64_t rows, const uint64_t* qoff,
     size_t tb = tmpBytes;
     SH_HIP(rocprim::segmented_radix_sort_keys(tmp, tb, (const uint64_t*)k0, k1, (unsigned)rows, nhuge, bi, ei, 0, 36,
                                               st));
-    hipLaunchKernelGGL(kDecodeBig, dim3(std::min<uint32_t>(nhuge, 65536)), dim3(256), 0, st, k1, qoff, huge, nhuge,
-                       qidBase, starts, nrec, out);
+    hipLaunchKernelGGL(kDecodeBig<COMPACT>, dim3(std::min<uint32_t>(nhuge, 65536)), dim3(256), 0, st, k1, qoff, huge,
+                       nhuge, qidBase, starts, nrec, out);
     SH_HIP(hipGetLastError());
+}
+
+void sortDecode(uint64_t* k0, uint64_t* k1, uint64_t rows, const uint64_t* qoff, uint32_t nq, const uint32_t* big,
+                uint32_t nbig, const uint32_t* huge, uint32_t nhuge, uint64_t qidBase, const uint64_t* starts,
+                uint32_t nrec, sahara_hit* out, void* tmp, size_t tmpBytes, hipStream_t st) {
+    sortInto<false>(k0, k1, rows, qoff, nq, big, nbig, huge, nhuge, qidBase, starts, nrec, out, tmp, tmpBytes, st);
+}
+
+void sortCompact(uint64_t* k0, uint64_t* k1, uint64_t rows, const uint64_t* qoff, uint32_t nq, const uint32_t* big,
+                 uint32_t nbig, const uint32_t* huge, uint32_t nhuge, uint64_t* out, void* tmp, size_t tmpBytes,
+                 hipStream_t st) {
+    sortInto<true>(k0, k1, rows, qoff, nq, big, nbig, huge, nhuge, 0, nullptr, 0, out, tmp, tmpBytes, st);
 }
 
 void launchPackPatterns3(const uint8_t* src, uint64_t npat, uint32_t m, uint32_t patBlocks, uint4* dst,
