@@ -96,7 +96,10 @@ typedef struct sahara_stats {
     uint64_t upload_chunks[3];   /* streamed upload chunks sent at 2 / 4 / 8 bits per symbol */
     uint64_t text_pos_tasks;     /* text tasks that came with their text position from the k-mer table (count=1) */
     uint64_t text_stolen;        /* nodes taken by idle lanes from busy lanes of their wave (count=1) */
-    uint64_t reserved[8];        /* zero: room for counters added later without changing the struct's size */
+    uint64_t best_rounds;        /* besthits: rounds per batch of the last call (0: not a besthits pass) */
+    uint64_t best_skipped;       /* besthits: work items dropped because their pattern had reported in an
+                                  * earlier round (count=1) */
+    uint64_t reserved[6];        /* zero: room for counters added later without changing the struct's size */
 } sahara_stats;
 
 const char* sahara_gpu_last_error(void);
@@ -228,6 +231,30 @@ int  sahara_gpu_search_best(void* ctx, const uint8_t* ranks, uint64_t n_patterns
                             const uint32_t* pi, const uint32_t* l, const uint32_t* u,
                             const uint32_t* n_searches, uint32_t n_schemes, uint32_t max_hits,
                             sahara_hit** hits, uint64_t* n_hits);
+/* besthits from the reads themselves, the twins of sahara_gpu_search_reads,
+ * _packed and _packed_compact: the same arguments, with the schemes given as
+ * in sahara_gpu_search_best and edit operations always on; the same hits as
+ * sahara_gpu_search_best over the interleaved patterns. On a single-part
+ * index all four calls make one streamed pass: each batch of queries runs the
+ * schemes as rounds on the device, round j seeding only the queries that had
+ * no located row after round j - 1, and is located, sorted and handed to the
+ * host once (sahara_stats.best_rounds = n_schemes). On a multi-part index
+ * (and with SAHARA_BEST_HOST=1, the A/B and parity hook) the whole hits come
+ * from a host loop of one device-resident pass per scheme; the compact call
+ * needs a single-part index and at most 15 errors, as its twin. */
+int  sahara_gpu_search_best_reads(void* ctx, const uint8_t* reads, uint64_t n_reads, uint32_t len, int reverse,
+                                  uint64_t limit, const uint32_t* pi, const uint32_t* l, const uint32_t* u,
+                                  const uint32_t* n_searches, uint32_t n_schemes, uint32_t max_hits,
+                                  sahara_hit** hits, uint64_t* n_hits);
+int  sahara_gpu_search_best_packed(void* ctx, const uint8_t* codes, uint64_t sym0, const uint64_t* n_pos,
+                                   uint64_t n_count, uint64_t n_reads, uint32_t len, int reverse, uint64_t limit,
+                                   const uint32_t* pi, const uint32_t* l, const uint32_t* u,
+                                   const uint32_t* n_searches, uint32_t n_schemes, uint32_t max_hits,
+                                   sahara_hit** hits, uint64_t* n_hits);
+int  sahara_gpu_search_best_packed_compact(void* ctx, const uint8_t* codes, uint64_t sym0, const uint64_t* n_pos,
+                                           uint64_t n_count, uint64_t n_reads, uint32_t len, int reverse,
+                                           uint64_t limit, const uint32_t* pi, const uint32_t* l, const uint32_t* u,
+                                           const uint32_t* n_searches, uint32_t n_schemes, sahara_hit_blocks* out);
 
 /* Device-resident form of the same path for benchmarking: stage patterns and
  * scheme once, run search+locate+sort with results left in HBM, fetch later. */

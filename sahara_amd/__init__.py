@@ -21,7 +21,8 @@ import numpy as np
 
 __all__ = [
     "BiFMIndex", "HIT_DTYPE", "search", "search_reads", "search_reads_compact", "CompactHits", "PackedReads",
-    "pack_reads", "search_packed", "search_packed_compact", "read_fasta", "search_scheme", "scheme_parts",
+    "pack_reads", "search_packed", "search_packed_compact", "search_best", "search_best_reads", "search_best_packed",
+    "search_best_packed_compact", "read_fasta", "search_scheme", "scheme_parts",
     "scheme_generators",
     "scheme_counts", "synth_reference", "synth_reads", "interleave_rc", "load_fasta",
     "library_path", "lib", "SaharaError", "DNA5", "DNA4",
@@ -78,7 +79,8 @@ class Stats(C.Structure):
                 ("seed_ms", C.c_double), ("text_steps", C.c_uint64), ("stage_ms", C.c_double),
                 ("output_ms", C.c_double), ("text_launches", C.c_uint64),
                 ("upload_chunks", C.c_uint64 * 3), ("text_pos_tasks", C.c_uint64),
-                ("text_stolen", C.c_uint64), ("reserved", C.c_uint64 * 8)]
+                ("text_stolen", C.c_uint64), ("best_rounds", C.c_uint64), ("best_skipped", C.c_uint64),
+                ("reserved", C.c_uint64 * 6)]
 
     def as_dict(self):
         return {n: (list(v) if isinstance(v, C.Array) else v) for n, v in
@@ -125,6 +127,15 @@ EXPORTED = {
     "sahara_gpu_search_best": (C.c_int, [C.c_void_p, u8p, C.c_uint64, C.c_uint32, u32p, u32p, u32p,
                                          u32p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p),
                                          C.POINTER(C.c_uint64)]),
+    "sahara_gpu_search_best_reads": (C.c_int, [C.c_void_p, u8p, C.c_uint64, C.c_uint32, C.c_int, C.c_uint64, u32p,
+                                               u32p, u32p, u32p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p),
+                                               C.POINTER(C.c_uint64)]),
+    "sahara_gpu_search_best_packed": (C.c_int, [C.c_void_p, u8p, C.c_uint64, u64p, C.c_uint64, C.c_uint64, C.c_uint32,
+                                                C.c_int, C.c_uint64, u32p, u32p, u32p, u32p, C.c_uint32, C.c_uint32,
+                                                C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
+    "sahara_gpu_search_best_packed_compact": (C.c_int, [C.c_void_p, u8p, C.c_uint64, u64p, C.c_uint64, C.c_uint64,
+                                                        C.c_uint32, C.c_int, C.c_uint64, u32p, u32p, u32p, u32p,
+                                                        C.c_uint32, C.POINTER(HitBlocks)]),
     "sahara_gpu_stage": (C.c_int, [C.c_void_p, u8p, C.c_uint64, C.c_uint32, u32p, u32p, u32p,
                                    C.c_uint32, C.c_int]),
     "sahara_gpu_run": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]),
@@ -643,17 +654,68 @@ def search_best(index, queries, schemes, max_hits=0):
     q = np.ascontiguousarray(queries, dtype=np.uint8)
     if q.ndim != 2 or q.shape[0] == 0:
         raise SaharaError("queries must be a non-empty (n_patterns, len) array")
-    def cat(i):
-        parts = [np.asarray(s[i], np.uint32).ravel() for s in schemes] or [np.zeros(1, np.uint32)]
-        return np.ascontiguousarray(np.concatenate(parts))
-    pi, l, u = cat(0), cat(1), cat(2)
-    ns = np.array([len(s[0]) for s in schemes], np.uint32)
+    pi, l, u, ns = _best_schemes(schemes)
     out = C.c_void_p()
     n = C.c_uint64()
     _check(lib().sahara_gpu_search_best(index._h, _p(q, u8p), q.shape[0], q.shape[1], _p(pi, u32p),
                                         _p(l, u32p), _p(u, u32p), _p(ns, u32p), len(schemes), max_hits,
                                         C.byref(out), C.byref(n)))
     return _hits_array(out, n.value)
+
+
+def _best_schemes(schemes):
+    """(pi, l, u, rows per scheme) of a besthits scheme list, each array the schemes back to back."""
+    def cat(i):
+        parts = [np.asarray(s[i], np.uint32).ravel() for s in schemes] or [np.zeros(1, np.uint32)]
+        return np.ascontiguousarray(np.concatenate(parts))
+    return cat(0), cat(1), cat(2), np.array([len(s[0]) for s in schemes] or [0], np.uint32)
+
+
+def search_best_reads(index, reads, schemes, reverse=True, limit=0, max_hits=0):
+    """search_best from the reads themselves (sahara_gpu_search_best_reads):
+    the reverse-complement interleave and, on a single-part index, the rounds
+    over the schemes run on the device. Arguments as search_reads, `schemes`
+    as search_best; the same hits as search_best over the interleaved
+    patterns."""
+    r = np.ascontiguousarray(reads, dtype=np.uint8)
+    if r.ndim != 2 or r.shape[0] == 0:
+        raise SaharaError("reads must be a non-empty (n_reads, len) array")
+    pi, l, u, ns = _best_schemes(schemes)
+    out = C.c_void_p()
+    n = C.c_uint64()
+    _check(lib().sahara_gpu_search_best_reads(index._h, _p(r, u8p), r.shape[0], r.shape[1], int(reverse), int(limit),
+                                              _p(pi, u32p), _p(l, u32p), _p(u, u32p), _p(ns, u32p), len(schemes),
+                                              max_hits, C.byref(out), C.byref(n)))
+    return _hits_array(out, n.value)
+
+
+def _best_packed_args(packed):
+    if packed.n_reads <= 0:
+        raise SaharaError("no reads")
+    return (_p(packed.codes, u8p), packed.sym0, _p(packed.n_pos, u64p) if packed.n_pos.size else None,
+            packed.n_pos.size, packed.n_reads, packed.length)
+
+
+def search_best_packed(index, packed, schemes, reverse=True, limit=0, max_hits=0):
+    """search_best_reads from PackedReads (sahara_gpu_search_best_packed)."""
+    pi, l, u, ns = _best_schemes(schemes)
+    out = C.c_void_p()
+    n = C.c_uint64()
+    _check(lib().sahara_gpu_search_best_packed(index._h, *_best_packed_args(packed), int(reverse), int(limit),
+                                               _p(pi, u32p), _p(l, u32p), _p(u, u32p), _p(ns, u32p), len(schemes),
+                                               max_hits, C.byref(out), C.byref(n)))
+    return _hits_array(out, n.value)
+
+
+def search_best_packed_compact(index, packed, schemes, reverse=True, limit=0):
+    """search_best_packed (max_hits = 0) with the hits as compact records
+    (sahara_gpu_search_best_packed_compact): `sahara search -m besthits`'s call."""
+    pi, l, u, ns = _best_schemes(schemes)
+    b = HitBlocks()
+    _check(lib().sahara_gpu_search_best_packed_compact(index._h, *_best_packed_args(packed), int(reverse), int(limit),
+                                                       _p(pi, u32p), _p(l, u32p), _p(u, u32p), _p(ns, u32p),
+                                                       len(schemes), C.byref(b)))
+    return CompactHits(b, index)
 
 
 def scheme_generators():

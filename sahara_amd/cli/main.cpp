@@ -461,7 +461,7 @@ int cmdSearch(int argc, char** argv) {
     // the queries (sahara_gpu_prepare): the sink is pinned while the index
     // loads, the buffers once it is resident. Compact records only, <= 2
     // devices (the library's pool keeps two idle sinks).
-    const bool prepare = !besthits && mh <= 0 && ngpu <= 2;
+    const bool prepare = mh <= 0 && ngpu <= 2;
     const QueryEstimate qe = prepare ? estimateQueries(query.value) : QueryEstimate{};
     uint64_t npatEst = (noRev.given ? 1 : 2) * qe.reads;
     if (limit.given) npatEst = std::min<uint64_t>(npatEst, toU64(limit.value, "--limit_queries"));
@@ -481,20 +481,19 @@ int cmdSearch(int argc, char** argv) {
 
     // queries (search.cpp:111-130): parsed and verified on the host (parallel
     // whole-file ingest) straight into two bits per symbol with the N
-    // positions listed (besthits: one rank per byte); the reverse-complement
-    // interleave and --limit_queries cut happen on the device
-    // (sahara_gpu_search_packed[_compact]), so only the packed reads cross
-    // PCIe. Query numbers in messages count the interleaved list.
+    // positions listed; the reverse-complement interleave and
+    // --limit_queries cut happen on the device
+    // (sahara_gpu_search[_best]_packed[_compact]), so only the packed reads
+    // cross PCIe. Query numbers in messages count the interleaved list.
     // (the library's ingest, sahara_read_fasta: the 2-bit form lands in
     // page-locked memory, which the search calls DMA without a copy)
     const unsigned nt = hostThreads();
-    const bool packedIn = !besthits;
     struct Queries {
         sahara_fasta f{};
         ~Queries() { sahara_free_fasta(&f); }
         size_t records() const { return f.n_records; }
     } Q;
-    check(sahara_read_fasta(query.value.c_str(), (uint32_t)sigma, packedIn ? 2 : 1, nt, &Q.f), "reading queries");
+    check(sahara_read_fasta(query.value.c_str(), (uint32_t)sigma, 2, nt, &Q.f), "reading queries");
     const size_t nrec = Q.records();
     const size_t per = noRev.given ? 1 : 2;  // patterns per read
     if (Q.f.bad) {
@@ -560,7 +559,7 @@ int cmdSearch(int argc, char** argv) {
             throw CliError(fmtStr("query %zu has length %zu, but all queries must have the length of the first "
                                   "(%u): sahara expands one search scheme for queries[0].size()",
                                   per * r, (size_t)(qoffs[r + 1] - qoffs[r]), len));
-    const uint8_t* reads = Q.f.data;  // nreads x len, back to back (packedIn: 2-bit codes)
+    const uint8_t* reads = Q.f.data;  // nreads x len, back to back, as 2-bit codes
 
     std::vector<Scheme> schemes;  // all: [0..k]; besthits: one per exact error count j
     // --dynamic_generator: part sizes by weighted node count (search.cpp:192-195, 202-205)
@@ -606,10 +605,19 @@ int cmdSearch(int argc, char** argv) {
     }
     timing.emplace_back("searchScheme", sw.reset());
 
-    // hits as compact records where they apply (all mode without --max_hits,
-    // one index part, <= 15 errors; SAHARA_CLI_FULL_HITS=1: whole records)
+    // hits as compact records where they apply (no --max_hits, one index
+    // part, <= 15 errors; SAHARA_CLI_FULL_HITS=1: whole records)
     const char* fullEnv = std::getenv("SAHARA_CLI_FULL_HITS");
-    const bool compactOut = !besthits && mh <= 0 && info.n_parts == 1 && k <= 15 && !(fullEnv && std::atoi(fullEnv));
+    const bool compactOut = mh <= 0 && info.n_parts == 1 && k <= 15 && !(fullEnv && std::atoi(fullEnv));
+    // besthits: the exact-j schemes back to back (sahara_gpu_search_best's form)
+    std::vector<uint32_t> bestPi, bestL, bestU, bestNs;
+    if (besthits)
+        for (const Scheme& s : schemes) {
+            bestPi.insert(bestPi.end(), s.pi.begin(), s.pi.end());
+            bestL.insert(bestL.end(), s.l.begin(), s.l.end());
+            bestU.insert(bestU.end(), s.u.begin(), s.u.end());
+            bestNs.push_back(s.n);
+        }
     // search + locate (search.cpp:218-250), reads sharded over the devices
     // (a read and its reverse complement stay together; qids stay global)
     std::vector<HitPart> parts(ngpu);
@@ -643,26 +651,18 @@ int cmdSearch(int argc, char** argv) {
                     rc = sahara_gpu_search_packed(ctx[g], reads, (uint64_t)r0 * len, npos, ncount, r1 - r0, len,
                                                   noRev.given ? 0 : 1, q1 - q0, s.pi.data(), s.l.data(), s.u.data(),
                                                   s.n, edit ? 1 : 0, cap, &hits, &nh);
-                } else {  // search_best takes the interleaved patterns
-                    std::vector<uint8_t> pats((q1 - q0) * len);
-                    for (size_t q = q0; q < q1; ++q) {
-                        const uint8_t* src = reads + (q / per) * len;
-                        uint8_t* dst = pats.data() + (q - q0) * len;
-                        if (per == 2 && (q & 1)) {
-                            for (uint32_t j = 0; j < len; ++j) dst[j] = complementRank(src[len - 1 - j], (uint32_t)sigma);
-                        } else {
-                            std::memcpy(dst, src, len);
-                        }
-                    }
-                    std::vector<uint32_t> pi, l, u, ns;
-                    for (const Scheme& s : schemes) {
-                        pi.insert(pi.end(), s.pi.begin(), s.pi.end());
-                        l.insert(l.end(), s.l.begin(), s.l.end());
-                        u.insert(u.end(), s.u.begin(), s.u.end());
-                        ns.push_back(s.n);
-                    }
-                    rc = sahara_gpu_search_best(ctx[g], pats.data(), q1 - q0, len, pi.data(), l.data(), u.data(),
-                                                ns.data(), (uint32_t)ns.size(), cap, &hits, &nh);
+                } else if (compactOut) {  // the schemes as rounds on the device, the hits as for all-mode
+                    rc = sahara_gpu_search_best_packed_compact(ctx[g], reads, (uint64_t)r0 * len, npos, ncount,
+                                                               r1 - r0, len, noRev.given ? 0 : 1, q1 - q0,
+                                                               bestPi.data(), bestL.data(), bestU.data(),
+                                                               bestNs.data(), (uint32_t)bestNs.size(), &part.blocks);
+                    part.compact = rc == 0;
+                    nh = part.blocks.n_hits;
+                } else {
+                    rc = sahara_gpu_search_best_packed(ctx[g], reads, (uint64_t)r0 * len, npos, ncount, r1 - r0, len,
+                                                       noRev.given ? 0 : 1, q1 - q0, bestPi.data(), bestL.data(),
+                                                       bestU.data(), bestNs.data(), (uint32_t)bestNs.size(), cap,
+                                                       &hits, &nh);
                 }
                 if (rc != 0) {
                     errs[g] = sahara_gpu_last_error();

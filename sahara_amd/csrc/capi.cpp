@@ -432,7 +432,7 @@ int sahara_gpu_save(void* ctx, const char* path) {
 
 int sahara_gpu_stage(void* ctx, const uint8_t* ranks, uint64_t n_patterns, uint32_t len, const uint32_t* pi,
                      const uint32_t* l, const uint32_t* u, uint32_t n_searches, int edit) {
-    return guarded([&] { stage(ctxOf(ctx), ranks, n_patterns, len, pi, l, u, n_searches, edit); });
+    return guarded([&] { stage(ctxOf(ctx), ranks, n_patterns, len, pi, l, u, &n_searches, 1, edit); });
 }
 
 int sahara_gpu_run(void* ctx, int count, uint64_t* n_hits) {
@@ -701,15 +701,28 @@ static void abandonCall(Ctx* c, bool packingOnly) {
 // sahara_gpu_search / sahara_gpu_search_reads: streamed upload, the pipelined
 // pass, the hits streamed into a pinned host sink batch by batch, then handed
 // to the caller (search.cpp:218-250 from host queries to host hits).
+// The scheme(s) of a call: one, or the exact-j schemes of a besthits call back
+// to back, which the pass runs as rounds within each batch (pass.cpp).
+struct Schemes {
+    const uint32_t *pi, *l, *u;
+    const uint32_t* ns;  // rows of each
+    uint32_t n;
+    int edit;
+    uint64_t rows() const {
+        uint64_t t = 0;
+        for (uint32_t j = 0; j < n; ++j) t += ns[j];
+        return t;
+    }
+};
+
 static void searchStreamed(Ctx* c, const uint8_t* src, uint64_t rows, bool rc, uint64_t npat, uint32_t len,
-                           const uint32_t* pi, const uint32_t* l, const uint32_t* u, uint32_t n_searches, int edit,
-                           uint32_t max_hits, sahara_hit** hits, uint64_t* n_hits,
+                           const Schemes& sc, uint32_t max_hits, sahara_hit** hits, uint64_t* n_hits,
                            const PackedReads* packed = nullptr) {
     using clk = std::chrono::steady_clock;
     const auto tA = clk::now();
     traceBegin(c, tA);
     HostBuf sink(nullptr, freeHits);
-    stageStreamed(c, src, rows, rc, npat, len, pi, l, u, n_searches, edit, packed);
+    stageStreamed(c, src, rows, rc, npat, len, sc.pi, sc.l, sc.u, sc.ns, sc.n, sc.edit, packed);
     ScopeExit failed([c] { abandonCall(c, false); });
     const auto tB = clk::now();
     // --max_hits: per batch on the device (limitBatch), so the limited hits
@@ -803,8 +816,8 @@ int sahara_gpu_search(void* ctx, const uint8_t* ranks, uint64_t n_patterns, uint
                       const uint32_t* l, const uint32_t* u, uint32_t n_searches, int edit, uint32_t max_hits,
                       sahara_hit** hits, uint64_t* n_hits) {
     return guarded([&] {
-        searchStreamed(ctxOf(ctx), ranks, n_patterns, false, n_patterns, len, pi, l, u, n_searches, edit, max_hits,
-                       hits, n_hits);
+        searchStreamed(ctxOf(ctx), ranks, n_patterns, false, n_patterns, len, Schemes{pi, l, u, &n_searches, 1, edit},
+                       max_hits, hits, n_hits);
     });
 }
 
@@ -815,7 +828,8 @@ int sahara_gpu_search_reads(void* ctx, const uint8_t* reads, uint64_t n_reads, u
         Ctx* c = ctxOf(ctx);
         if (c->I.sigma != 5 && c->I.sigma != 6) throw Error("reverse complements need a dna4 or dna5 index");
         const ReadRows R = readRows(reverse, n_reads, limit);
-        searchStreamed(c, reads, R.rows, reverse != 0, R.npat, len, pi, l, u, n_searches, edit, max_hits, hits, n_hits);
+        searchStreamed(c, reads, R.rows, reverse != 0, R.npat, len, Schemes{pi, l, u, &n_searches, 1, edit}, max_hits,
+                       hits, n_hits);
     });
 }
 
@@ -823,8 +837,7 @@ int sahara_gpu_search_reads(void* ctx, const uint8_t* reads, uint64_t n_reads, u
 // written as 8-B records by the device into a pinned host sink (pass.cpp
 // finish), handed over as blocks (one per batch).
 static void searchReadsCompact(Ctx* c, const uint8_t* reads, uint64_t n_reads, uint32_t len, int reverse,
-                               uint64_t limit, const uint32_t* pi, const uint32_t* l, const uint32_t* u,
-                               uint32_t n_searches, int edit, sahara_hit_blocks* out,
+                               uint64_t limit, const Schemes& sc, sahara_hit_blocks* out,
                                const PackedReads* packed = nullptr) {
     using clk = std::chrono::steady_clock;
     const auto tA = clk::now();
@@ -832,10 +845,10 @@ static void searchReadsCompact(Ctx* c, const uint8_t* reads, uint64_t n_reads, u
     if (!c->more.empty()) throw Error("compact hit records need a single-part index (text < 2^32 symbols)");
     const ReadRows R = readRows(reverse, n_reads, limit);
     traceBegin(c, tA);
-    for (uint64_t i = 0; i < (uint64_t)n_searches * len; ++i)  // before staging: a refused call stages nothing
-        if (u[i] > 15) throw Error("compact hit records hold at most 15 errors");
+    for (uint64_t i = 0, n = sc.rows() * len; i < n; ++i)  // before staging: a refused call stages nothing
+        if (sc.u[i] > 15) throw Error("compact hit records hold at most 15 errors");
     HostBuf recs(nullptr, freeHits);
-    stageStreamed(c, reads, R.rows, reverse != 0, R.npat, len, pi, l, u, n_searches, edit, packed);
+    stageStreamed(c, reads, R.rows, reverse != 0, R.npat, len, sc.pi, sc.l, sc.u, sc.ns, sc.n, sc.edit, packed);
     // (until the pass starts only the packing can be reading the caller's reads)
     bool passStarted = false;
     ScopeExit failed([&] { abandonCall(c, !passStarted); });
@@ -913,7 +926,7 @@ int sahara_gpu_search_reads_compact(void* ctx, const uint8_t* reads, uint64_t n_
     return guarded([&] {
         if (!out) throw Error("sahara_gpu_search_reads_compact: null output");
         *out = sahara_hit_blocks{};
-        searchReadsCompact(ctxOf(ctx), reads, n_reads, len, reverse, limit, pi, l, u, n_searches, edit, out);
+        searchReadsCompact(ctxOf(ctx), reads, n_reads, len, reverse, limit, Schemes{pi, l, u, &n_searches, 1, edit}, out);
     });
 }
 
@@ -926,8 +939,8 @@ int sahara_gpu_search_packed(void* ctx, const uint8_t* codes, uint64_t sym0, con
         if (!codes || (n_count && !n_pos)) throw Error("sahara_gpu_search_packed: null input");
         const ReadRows R = readRows(reverse, n_reads, limit);
         const PackedReads pk{sym0, n_pos, n_count};
-        searchStreamed(c, codes, R.rows, reverse != 0, R.npat, len, pi, l, u, n_searches, edit, max_hits, hits, n_hits,
-                       &pk);
+        searchStreamed(c, codes, R.rows, reverse != 0, R.npat, len, Schemes{pi, l, u, &n_searches, 1, edit}, max_hits,
+                       hits, n_hits, &pk);
     });
 }
 
@@ -940,7 +953,8 @@ int sahara_gpu_search_packed_compact(void* ctx, const uint8_t* codes, uint64_t s
         *out = sahara_hit_blocks{};
         if (!codes || (n_count && !n_pos)) throw Error("sahara_gpu_search_packed_compact: null input");
         const PackedReads pk{sym0, n_pos, n_count};
-        searchReadsCompact(ctxOf(ctx), codes, n_reads, len, reverse, limit, pi, l, u, n_searches, edit, out, &pk);
+        searchReadsCompact(ctxOf(ctx), codes, n_reads, len, reverse, limit, Schemes{pi, l, u, &n_searches, 1, edit}, out,
+                           &pk);
     });
 }
 
@@ -1001,59 +1015,167 @@ void sahara_gpu_free_blocks(sahara_hit_blocks* b) {
     *b = sahara_hit_blocks{};
 }
 
+// besthits on the host: a loop over the exact-j schemes, each a whole
+// device-resident pass over the patterns still without a hit, the found
+// patterns marked and the rest subset here (search_ng21::search_best,
+// search.cpp:233-241). The path of a multi-part index, where "found" is
+// decided across the parts, and of SAHARA_BEST_HOST=1 (A/B and parity hook);
+// a single-part index runs the schemes as rounds inside each batch of one
+// streamed pass (pass.cpp).
+static void bestOnHost(Ctx* c, const uint8_t* ranks, uint64_t n_patterns, uint32_t len, const Schemes& sc,
+                       uint32_t max_hits, sahara_hit** hits, uint64_t* n_hits) {
+    std::vector<uint64_t> todo(n_patterns);
+    for (uint64_t i = 0; i < n_patterns; ++i) todo[i] = i;
+    std::vector<uint8_t> sub;
+    std::vector<sahara_hit> all;
+    sahara_stats acc{};
+    uint64_t off = 0;
+    for (uint32_t j = 0; j < sc.n && !todo.empty(); off += (uint64_t)sc.ns[j] * len, ++j) {
+        const uint8_t* src = ranks;
+        if (todo.size() != n_patterns) {
+            sub.resize(todo.size() * len);
+            for (size_t i = 0; i < todo.size(); ++i)
+                std::memcpy(sub.data() + i * len, ranks + todo[i] * len, len);
+            src = sub.data();
+        }
+        stage(c, src, todo.size(), len, sc.pi + off, sc.l + off, sc.u + off, &sc.ns[j], 1, 1);
+        // --max_hits per batch on the device (single part; the host pass
+        // below is then a no-op on what is left)
+        c->sk.limitN = c->more.empty() ? max_hits : 0u;
+        {
+            const ScopeExit limitOff([c] { c->sk.limitN = 0; });
+            run(c, false);
+        }
+        std::vector<sahara_hit> v(c->nout);
+        if (c->nout) SH_HIP(hipMemcpy(v.data(), c->out.ptr, c->nout * sizeof(sahara_hit), hipMemcpyDeviceToHost));
+        acc.search_ms += c->stats.search_ms;
+        acc.locate_ms += c->stats.locate_ms;
+        acc.sort_ms += c->stats.sort_ms;
+        acc.total_ms += c->stats.total_ms;
+        acc.hits += c->stats.hits;
+        acc.patterns += c->stats.patterns;
+        std::vector<char> found(todo.size(), 0);
+        for (auto& h : v) {
+            found[h.qid] = 1;
+            h.qid = todo[h.qid];
+        }
+        all.insert(all.end(), v.begin(), v.end());
+        size_t w = 0;
+        for (size_t i = 0; i < todo.size(); ++i)
+            if (!found[i]) todo[w++] = todo[i];
+        todo.resize(w);
+    }
+    c->stats = acc;
+    std::sort(all.begin(), all.end(), hitLess);
+    if (max_hits) limitHits(all, max_hits);
+    handOver(all, hits, n_hits);
+}
+
+static bool bestHostForced() {
+    const char* e = std::getenv("SAHARA_BEST_HOST");
+    return e && std::atoi(e) != 0;
+}
+
+// The query list of a reads call as ranks on the host (the host loop's
+// input): the reads, given one rank per byte or (packed) two bits per symbol
+// with the N positions listed, interleaved with their reverse complements
+// (reverse) and cut to R.npat patterns.
+static std::vector<uint8_t> queryRanks(const Ctx* c, const uint8_t* src, uint32_t len, bool reverse, const ReadRows& R,
+                                       const PackedReads* packed) {
+    const uint32_t sigma = c->I.sigma;
+    if (sigma != 5 && sigma != 6) throw Error("reverse complements need a dna4 or dna5 index");
+    std::vector<uint8_t> reads;
+    if (packed) {
+        const uint8_t rankOf[4] = {1, 2, 3, (uint8_t)(sigma == 6 ? 5 : 4)};
+        reads.resize(R.rows * len);
+        for (uint64_t i = 0; i < reads.size(); ++i) {
+            const uint64_t s = packed->sym0 + i;
+            reads[i] = rankOf[(src[s / 4] >> (2 * (s % 4))) & 3u];
+        }
+        const uint64_t lo = packed->sym0, hi = lo + reads.size();
+        for (uint64_t i = 0; i < packed->nCount; ++i) {
+            if (i && packed->nPos[i] <= packed->nPos[i - 1])
+                throw Error("N positions of packed reads must be strictly ascending");
+            if (packed->nPos[i] < lo || packed->nPos[i] >= hi) continue;
+            if (sigma == 5) throw Error("pattern rank out of range for this index");  // N is no dna4 rank
+            reads[packed->nPos[i] - lo] = 4;
+        }
+        src = reads.data();
+    }
+    if (!reverse) return packed ? std::move(reads) : std::vector<uint8_t>(src, src + R.npat * len);
+    std::vector<uint8_t> both(2 * R.rows * len);
+    if (sahara_interleave_rc(src, R.rows, len, sigma, both.data()) != 0) throw Error(g_err);
+    both.resize(R.npat * len);
+    return both;
+}
+
+// The besthits twins of the reads calls: whole hits ...
+static void bestStreamed(Ctx* c, const uint8_t* src, uint64_t n_reads, uint32_t len, bool interleave, int reverse,
+                         uint64_t limit, const Schemes& sc, uint32_t max_hits, sahara_hit** hits, uint64_t* n_hits,
+                         const PackedReads* packed) {
+    if (!sc.n) throw Error("besthits: no schemes");
+    const ReadRows R = interleave ? readRows(reverse, n_reads, limit) : ReadRows{n_reads, n_reads};
+    if (R.npat == 0) throw Error("no patterns");
+    const bool rc = interleave && reverse != 0;
+    if (c->more.empty() && !bestHostForced()) {
+        if (interleave && !packed && c->I.sigma != 5 && c->I.sigma != 6)
+            throw Error("reverse complements need a dna4 or dna5 index");
+        return searchStreamed(c, src, R.rows, rc, R.npat, len, sc, max_hits, hits, n_hits, packed);
+    }
+    if (!interleave) return bestOnHost(c, src, R.npat, len, sc, max_hits, hits, n_hits);
+    const std::vector<uint8_t> ranks = queryRanks(c, src, len, rc, R, packed);
+    bestOnHost(c, ranks.data(), R.npat, len, sc, max_hits, hits, n_hits);
+}
+
 int sahara_gpu_search_best(void* ctx, const uint8_t* ranks, uint64_t n_patterns, uint32_t len, const uint32_t* pi,
                            const uint32_t* l, const uint32_t* u, const uint32_t* n_searches, uint32_t n_schemes,
                            uint32_t max_hits, sahara_hit** hits, uint64_t* n_hits) {
     return guarded([&] {
         Ctx* c = ctxOf(ctx);
         if (!n_schemes) throw Error("sahara_gpu_search_best: no schemes");
-        // search_ng21::search_best (search.cpp:233-241): scheme j holds exactly j
-        // errors; a pattern leaves the work list at the first j that reports.
-        std::vector<uint64_t> todo(n_patterns);
-        for (uint64_t i = 0; i < n_patterns; ++i) todo[i] = i;
-        std::vector<uint8_t> sub;
-        std::vector<sahara_hit> all;
-        sahara_stats acc{};
-        uint64_t off = 0;
-        for (uint32_t j = 0; j < n_schemes && !todo.empty(); off += (uint64_t)n_searches[j] * len, ++j) {
-            const uint8_t* src = ranks;
-            if (todo.size() != n_patterns) {
-                sub.resize(todo.size() * len);
-                for (size_t i = 0; i < todo.size(); ++i)
-                    std::memcpy(sub.data() + i * len, ranks + todo[i] * len, len);
-                src = sub.data();
-            }
-            stage(c, src, todo.size(), len, pi + off, l + off, u + off, n_searches[j], 1);
-            // --max_hits per batch on the device (single part; the host pass
-            // below is then a no-op on what is left)
-            c->sk.limitN = c->more.empty() ? max_hits : 0u;
-            {
-                const ScopeExit limitOff([c] { c->sk.limitN = 0; });
-                run(c, false);
-            }
-            std::vector<sahara_hit> v(c->nout);
-            if (c->nout) SH_HIP(hipMemcpy(v.data(), c->out.ptr, c->nout * sizeof(sahara_hit), hipMemcpyDeviceToHost));
-            acc.search_ms += c->stats.search_ms;
-            acc.locate_ms += c->stats.locate_ms;
-            acc.sort_ms += c->stats.sort_ms;
-            acc.total_ms += c->stats.total_ms;
-            acc.hits += c->stats.hits;
-            acc.patterns += c->stats.patterns;
-            std::vector<char> found(todo.size(), 0);
-            for (auto& h : v) {
-                found[h.qid] = 1;
-                h.qid = todo[h.qid];
-            }
-            all.insert(all.end(), v.begin(), v.end());
-            size_t w = 0;
-            for (size_t i = 0; i < todo.size(); ++i)
-                if (!found[i]) todo[w++] = todo[i];
-            todo.resize(w);
-        }
-        c->stats = acc;
-        std::sort(all.begin(), all.end(), hitLess);
-        if (max_hits) limitHits(all, max_hits);
-        handOver(all, hits, n_hits);
+        bestStreamed(c, ranks, n_patterns, len, false, 0, 0, Schemes{pi, l, u, n_searches, n_schemes, 1}, max_hits, hits,
+                     n_hits, nullptr);
+    });
+}
+
+int sahara_gpu_search_best_reads(void* ctx, const uint8_t* reads, uint64_t n_reads, uint32_t len, int reverse,
+                                 uint64_t limit, const uint32_t* pi, const uint32_t* l, const uint32_t* u,
+                                 const uint32_t* n_searches, uint32_t n_schemes, uint32_t max_hits, sahara_hit** hits,
+                                 uint64_t* n_hits) {
+    return guarded([&] {
+        Ctx* c = ctxOf(ctx);
+        if (!reads) throw Error("sahara_gpu_search_best_reads: null input");
+        bestStreamed(c, reads, n_reads, len, true, reverse, limit, Schemes{pi, l, u, n_searches, n_schemes, 1}, max_hits,
+                     hits, n_hits, nullptr);
+    });
+}
+
+int sahara_gpu_search_best_packed(void* ctx, const uint8_t* codes, uint64_t sym0, const uint64_t* n_pos,
+                                  uint64_t n_count, uint64_t n_reads, uint32_t len, int reverse, uint64_t limit,
+                                  const uint32_t* pi, const uint32_t* l, const uint32_t* u, const uint32_t* n_searches,
+                                  uint32_t n_schemes, uint32_t max_hits, sahara_hit** hits, uint64_t* n_hits) {
+    return guarded([&] {
+        Ctx* c = ctxOf(ctx);
+        if (!codes || (n_count && !n_pos)) throw Error("sahara_gpu_search_best_packed: null input");
+        const PackedReads pk{sym0, n_pos, n_count};
+        bestStreamed(c, codes, n_reads, len, true, reverse, limit, Schemes{pi, l, u, n_searches, n_schemes, 1}, max_hits,
+                     hits, n_hits, &pk);
+    });
+}
+
+// ... and compact records (single-part index: the rounds, always)
+int sahara_gpu_search_best_packed_compact(void* ctx, const uint8_t* codes, uint64_t sym0, const uint64_t* n_pos,
+                                          uint64_t n_count, uint64_t n_reads, uint32_t len, int reverse,
+                                          uint64_t limit, const uint32_t* pi, const uint32_t* l, const uint32_t* u,
+                                          const uint32_t* n_searches, uint32_t n_schemes, sahara_hit_blocks* out) {
+    return guarded([&] {
+        if (!out) throw Error("sahara_gpu_search_best_packed_compact: null output");
+        *out = sahara_hit_blocks{};
+        Ctx* c = ctxOf(ctx);
+        if (!codes || (n_count && !n_pos)) throw Error("sahara_gpu_search_best_packed_compact: null input");
+        if (!n_schemes) throw Error("besthits: no schemes");
+        const PackedReads pk{sym0, n_pos, n_count};
+        searchReadsCompact(c, codes, n_reads, len, reverse, limit, Schemes{pi, l, u, n_searches, n_schemes, 1}, out, &pk);
     });
 }
 

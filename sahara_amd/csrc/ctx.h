@@ -178,8 +178,18 @@ struct Ctx {
     uint64_t npat = 0;
     uint32_t m = 0, patWords = 0, patBlocks = 0;
     DevBuf<uint32_t> scheme, cover, kmerStart;        // FM scheme table; text table (textTable)
-    uint32_t nsearch = 0;
+    uint32_t nsearch = 0;                 // (several rounds: the most of any round, what the geometry is planned for)
     uint32_t maxErr = 0;
+    // The rounds of a pass (stageSchemes). Every call but besthits has one.
+    // A besthits call has one per exact-j scheme, their tables side by side in
+    // scheme / cover / kmerStart: round r's begin at its schemeAt / coverAt /
+    // kmerAt (words). Each batch runs the rounds in turn in its slot, a round
+    // seeding only the patterns that have not reported yet (pass.cpp issueFM).
+    struct Round {
+        uint32_t nsearch = 0, maxErr = 0;
+        size_t schemeAt = 0, coverAt = 0, kmerAt = 0;
+    };
+    std::vector<Round> rounds;
     bool edit = true;
     bool verify = true;
     bool locateSA = true;
@@ -346,6 +356,14 @@ struct Ctx {
         bool twoText = false;
         bool seedsInParts = false;        // seeds in parts: fmStart..seedDone0, then Ctx::partEv's pairs
         uint32_t seedParts = 0;           // (the later parts: Ctx::partEv[2 i], [2 i + 1] around part i)
+        // several rounds per batch: the last round records the events above
+        // (so the finisher waits for textDone as ever), round r before it
+        // earlier[r] (made by runPass before the pass's threads start)
+        struct RoundEvents {
+            Event fmStart{hipEventDefault}, seedDone{hipEventDefault}, fmBegin{hipEventDefault},
+                fmDone{hipEventDefault}, textStart{hipEventDefault}, textDone{hipEventDefault};
+        };
+        std::vector<RoundEvents> earlier;
     } slot[kSlots];
 
     // Streams, events and page-locked memory: declared last, released first
@@ -443,19 +461,21 @@ uint64_t pack2Avx2(const uint8_t* in, uint8_t* out, uint64_t count, uint32_t sig
                    std::vector<uint32_t>& exc);
 void uploadChunk(Ctx* c, hipStream_t kst);
 void ensureUploaded(Ctx* c, uint64_t patEnd, hipStream_t kst);
-void stageScheme(Ctx* c, uint64_t npat, uint32_t m, const uint32_t* pi, const uint32_t* l, const uint32_t* u,
-                 uint32_t ns, int edit);
+// (the scheme half of staging: nrounds schemes back to back, ns[r] rows each: Ctx::rounds)
+void stageSchemes(Ctx* c, uint64_t npat, uint32_t m, const uint32_t* pi, const uint32_t* l, const uint32_t* u,
+                  const uint32_t* ns, uint32_t nrounds, int edit);
 // reads given two bits per symbol (sahara_gpu_search_packed[_compact])
 struct PackedReads {
     uint64_t sym0;          // stream position of the first read's first symbol
     const uint64_t* nPos;   // stream positions of N, ascending (any outside the reads are ignored)
     uint64_t nCount;
 };
+// (nrounds schemes back to back, ns[r] rows each: one, or the rounds of a besthits call)
 void stageStreamed(Ctx* c, const uint8_t* src, uint64_t rows, bool rc, uint64_t npat, uint32_t m,
-                   const uint32_t* pi, const uint32_t* l, const uint32_t* u, uint32_t ns, int edit,
-                   const PackedReads* packed = nullptr);
+                   const uint32_t* pi, const uint32_t* l, const uint32_t* u, const uint32_t* ns, uint32_t nrounds,
+                   int edit, const PackedReads* packed = nullptr);
 void stage(Ctx* c, const uint8_t* ranks, uint64_t npat, uint32_t m, const uint32_t* pi, const uint32_t* l,
-           const uint32_t* u, uint32_t ns, int edit);
+           const uint32_t* u, const uint32_t* ns, uint32_t nrounds, int edit);
 
 // pass.cpp: one pass over the staged patterns (every part of the index)
 DeviceIndex& partOf(Ctx* c, uint32_t p);

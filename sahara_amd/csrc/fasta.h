@@ -438,12 +438,6 @@ inline FastaData parseFastaParallel(const std::string& path, uint32_t sigma, uns
     return D;
 }
 
-// ivs::reverse_complement_rank of one rank: A<->T, C<->G, N->N
-inline uint8_t complementRank(uint8_t c, uint32_t sigma) {
-    if (sigma == 6) return c == 1 ? 5 : c == 2 ? 3 : c == 3 ? 2 : c == 5 ? 1 : c;
-    return c == 1 ? 4 : c == 2 ? 3 : c == 3 ? 2 : c == 4 ? 1 : c;
-}
-
 inline std::vector<uint8_t> reverseComplement(const std::vector<uint8_t>& r, uint32_t sigma) {
     std::vector<uint8_t> o(r.size());
     for (size_t i = 0; i < r.size(); ++i) {

@@ -25,6 +25,8 @@ DeviceIndex& partOf(Ctx* c, uint32_t p) { return p == 0 ? c->I : c->more.at(p - 
 // host after the last part (no per-batch sink).
 void run(Ctx* c, bool count) {
     if (c->more.empty()) return runOne(c, count);
+    // (rounds mask a query by its rows in one part; "found" is decided across the parts: capi.cpp bestOnHost)
+    if (c->rounds.size() > 1) throw Error("a pass of several rounds needs a single-part index");
     const ScopeExit sinkBack([c, sink = c->sk.sink] { c->sk.sink = sink; });
     c->sk.sink = nullptr;
     sahara_stats T{};
@@ -47,6 +49,7 @@ void run(Ctx* c, bool count) {
         T.search_grid = S.search_grid;
         T.text_grid = S.text_grid;
         T.pipelined = S.pipelined;
+        T.best_rounds = S.best_rounds;
         for (uint64_t sahara_stats::*f :
              {&sahara_stats::batches, &sahara_stats::cursors, &sahara_stats::nodes, &sahara_stats::rank_nodes,
               &sahara_stats::ext_lines, &sahara_stats::lf_steps, &sahara_stats::text_nodes,
@@ -54,7 +57,7 @@ void run(Ctx* c, bool count) {
               &sahara_stats::text_active, &sahara_stats::text_refills, &sahara_stats::text_cycles_refill,
               &sahara_stats::text_cycles_step, &sahara_stats::text_cycles_emit, &sahara_stats::text_compare_steps,
               &sahara_stats::text_steps, &sahara_stats::text_launches,
-              &sahara_stats::text_pos_tasks, &sahara_stats::text_stolen})
+              &sahara_stats::text_pos_tasks, &sahara_stats::text_stolen, &sahara_stats::best_skipped})
             T.*f += S.*f;
         for (double sahara_stats::*f : {&sahara_stats::search_ms, &sahara_stats::locate_ms, &sahara_stats::sort_ms,
                                         &sahara_stats::text_ms, &sahara_stats::seed_ms})
@@ -154,6 +157,10 @@ static PassPlan makePlan(Ctx* c, bool count, bool redo) {
     const PassKnobs& k = P.k;
     const bool serial = P.serial = redo || !k.pipeline;
     P.count = count;
+    P.rounds = (uint32_t)c->rounds.size();
+    // (c->nsearch, c->maxErr: the worst round's, what stageSchemes left there)
+    const WorstRound worst = worstRound(c->rounds);
+    if (worst.nsearch != c->nsearch || worst.maxErr != c->maxErr) throw Error("staged rounds do not match their plan");
     const uint32_t sigma = c->I.sigma;
     P.fmLds = fmLdsBytes(c->nsearch, c->m, k.fmLdsDepth);
     const int fullBpc = searchBlocksPerCU(sigma, c->edit, P.fmLds);
@@ -207,7 +214,8 @@ static PassPlan makePlan(Ctx* c, bool count, bool redo) {
     // 792M -> 805M; without the split seeds a lone batch's early text phase
     // lost: C5 89.9M, C2 475M; profiles/r04_chunk_seeds_ab.txt).
     const bool chunkSeeds = c->sk.streaming && !serial && P.split && k.chunkSeeds;
-    P.early = !serial && P.split && (batchesHere > 1 || chunkSeeds);
+    // (several rounds: no early text launch, the first batch's rounds run like every other's)
+    P.early = !serial && P.split && (batchesHere > 1 || chunkSeeds) && P.rounds == 1;
     P.chunked0 = P.early && chunkSeeds;
     // a streamed call's finisher sleeps in its waits while the calling thread
     // and the pool pack (device-resident runs spin)
@@ -217,8 +225,9 @@ static PassPlan makePlan(Ctx* c, bool count, bool redo) {
     return P;
 }
 
-static SearchArgs searchArgs(Ctx* c, const PassPlan& P, Ctx::Slot& sl, uint64_t b) {
+static SearchArgs searchArgs(Ctx* c, const PassPlan& P, Ctx::Slot& sl, uint64_t b, uint32_t r) {
     const uint64_t q0 = P.bstart[b];
+    const Ctx::Round& R = c->rounds[r];
     SearchArgs a{};
     a.occF = c->I.occF.ptr;
     a.occR = c->I.occR.ptr;
@@ -227,12 +236,12 @@ static SearchArgs searchArgs(Ctx* c, const PassPlan& P, Ctx::Slot& sl, uint64_t 
     a.pats = c->pats.ptr + q0 * c->patWords;
     a.patWords = c->patWords;
     a.m = c->m;
-    a.nsearch = c->nsearch;
-    a.nitems = (uint32_t)((P.bstart[b + 1] - q0) * c->nsearch);
+    a.nsearch = R.nsearch;
+    a.nitems = (uint32_t)((P.bstart[b + 1] - q0) * R.nsearch);
     a.seeds = sl.seeds.ptr;
     a.seedItem = sl.seedItem.ptr;
     a.seedCount = sl.small.ptr + kSwSeedCount;
-    a.scheme = c->scheme.ptr;
+    a.scheme = c->scheme.ptr + R.schemeAt;
     a.work = sl.queues.ptr + kQueueSeeds;
     a.hitCount = sl.small.ptr + kSwHitCount;
     a.flags = sl.small.ptr + kSwFlags;
@@ -256,17 +265,18 @@ static SearchArgs searchArgs(Ctx* c, const PassPlan& P, Ctx::Slot& sl, uint64_t 
 
 // starting cursors; reference execution (verify off) ranks every node
 // from the root, so it does not use the k-mer table
-static SeedArgs seedArgs(Ctx* c, const PassPlan& P, Ctx::Slot& sl, uint64_t b) {
+static SeedArgs seedArgs(Ctx* c, const PassPlan& P, Ctx::Slot& sl, uint64_t b, uint32_t r) {
+    const Ctx::Round& R = c->rounds[r];
     SeedArgs sd{};
     sd.pats = c->pats.ptr + P.bstart[b] * c->patWords;
     sd.patWords = c->patWords;
-    sd.nsearch = c->nsearch;
-    sd.nitems = (uint32_t)((P.bstart[b + 1] - P.bstart[b]) * c->nsearch);
+    sd.nsearch = R.nsearch;
+    sd.nitems = (uint32_t)((P.bstart[b + 1] - P.bstart[b]) * R.nsearch);
     sd.n = (uint32_t)c->I.n;
     sd.kmer = c->verify && c->I.kmerK ? c->I.kmer.ptr : nullptr;
     sd.kmerK = c->I.kmerK;
     sd.kmerPos = c->I.kmerPos && P.k.kmerPos ? 1u : 0u;
-    sd.kmerStart = c->kmerStart.ptr;
+    sd.kmerStart = c->kmerStart.ptr + R.kmerAt;
     sd.seeds = sl.seeds.ptr;
     sd.seedItem = sl.seedItem.ptr;
     sd.seedCount = sl.small.ptr + kSwSeedCount;
@@ -277,13 +287,16 @@ static SeedArgs seedArgs(Ctx* c, const PassPlan& P, Ctx::Slot& sl, uint64_t b) {
     sd.taskCount = sl.small.ptr + kSwTaskCount;
     sd.flags = sl.small.ptr + kSwFlags;
     sd.counters = P.count ? c->counters.ptr : nullptr;
+    // a later round seeds only the patterns without a row so far (issueFM)
+    sd.skip = r ? sl.qcnt.ptr : nullptr;
     return sd;
 }
 
 // the launch over all of the batch's tasks (an early first batch's two
 // launches change taskBegin, taskCount and work: issueText)
-static TextBatchArgs textArgs(Ctx* c, const PassPlan& P, Ctx::Slot& sl, uint64_t b) {
+static TextBatchArgs textArgs(Ctx* c, const PassPlan& P, Ctx::Slot& sl, uint64_t b, uint32_t r) {
     const uint64_t q0 = P.bstart[b];
+    const Ctx::Round& R = c->rounds[r];
     TextBatchArgs t{};
     t.sa = c->I.saFull.ptr;
     t.text3 = c->I.text3.ptr;
@@ -292,10 +305,13 @@ static TextBatchArgs textArgs(Ctx* c, const PassPlan& P, Ctx::Slot& sl, uint64_t
     t.text3Bytes = (uint32_t)std::min<uint64_t>(text3Blocks(c->I.n) * 16, 0xFFFFFF00ull);
     t.pats3Bytes = (uint32_t)std::min<uint64_t>((P.bstart[b + 1] - q0) * c->patBlocks * 16, 0xFFFFFF00ull);
     t.m = c->m;
-    t.nsearch = c->nsearch;
-    t.table = reinterpret_cast<const uint2*>(c->cover.ptr);
+    t.nsearch = R.nsearch;
+    t.table = reinterpret_cast<const uint2*>(c->cover.ptr + R.coverAt);
     t.tasks = sl.tasks.ptr;
     t.taskCount = sl.small.ptr + kSwTaskCount;
+    // a later round's tasks follow the earlier rounds' in the slot's list
+    // (search indices of its own table): from kRoundReset's snapshot on
+    t.taskBegin = r ? sl.small.ptr + kSwRoundTasks : nullptr;
     t.taskCap = c->taskCap;
     t.work = sl.queues.ptr + kQueueSeedTasks;
     t.hits = sl.hits.ptr;
@@ -314,7 +330,7 @@ static TextBatchArgs textArgs(Ctx* c, const PassPlan& P, Ctx::Slot& sl, uint64_t
     t.qcnt = sl.qcnt.ptr;
     t.rank = sl.rank.ptr;
     t.probe = P.probe ? 1u : 0u;
-    t.isFirst = b == 0 ? 1u : 0u;
+    t.isFirst = b == 0 && r == 0 ? 1u : 0u;
     return t;
 }
 
@@ -369,19 +385,51 @@ struct Pass {
         SH_HIP(hipMemcpyAsync(sl.small.ptr + kSwSeedTasks, sl.small.ptr + kSwTaskCount, 4, hipMemcpyDeviceToDevice, sD));
     }
 
-    void issueFM(uint64_t b) {
+    // The events round r of the slot's batch records: the slot's own for the
+    // last round (finish waits for its textDone), sl.earlier[r] before it.
+    struct RoundEv {
+        hipEvent_t fmStart, seedDone, fmBegin, fmDone, textStart, textDone;
+    };
+    RoundEv eventsOf(Ctx::Slot& sl, uint32_t r) const {
+        if (r + 1 == P.rounds) return {sl.fmStart, sl.seedDone, sl.fmBegin, sl.fmDone, sl.textStart, sl.textDone};
+        Ctx::Slot::RoundEvents& e = sl.earlier[r];
+        return {e.fmStart, e.seedDone, e.fmBegin, e.fmDone, e.textStart, e.textDone};
+    }
+
+    // Round r of batch b: its seeds (sD) and FM phase (sA); issueText(b, r)
+    // follows. The event chain of a batch of several rounds, all in its slot:
+    //   free -> [sD] seeds(0) -> [sA] FM(0) -> [sB] text(0) -> textDone(0)
+    //        -> [sD] round reset, seeds(1, skip = qcnt) -> [sA] FM(1) -> [sB] text(1) -> textDone(1) -> ...
+    //        -> textDone(last) -> [sC] finish.
+    // Round r's seeds wait for round r - 1's textDone: they read the slot's
+    // per-query row counts as their mask, which the FM and text kernels of
+    // round r - 1 add to until then; nothing writes them while the seeds run,
+    // as round r's FM phase waits for the seeds. (Without that wait a query
+    // found late in round r - 1 would be searched again: silently wrong hits.)
+    // The reset of the seed count and the queue words sits behind the same
+    // wait, so no kernel of round r - 1 still reads them.
+    void issueFM(uint64_t b, uint32_t r) {
         Ctx::Slot& sl = slotOf(b);
         const std::vector<uint64_t>& bstart = P.bstart;
-        reserveSlot(c, sl);
-        SH_HIP(hipStreamWaitEvent(sA, sl.free, 0));  // the slot's previous batch is fully consumed
-        const uint32_t nitems = (uint32_t)((bstart[b + 1] - bstart[b]) * c->nsearch);
-        sl.seeds.reserve(nitems);
-        sl.seedItem.reserve(nitems);
-        const SearchArgs a = searchArgs(c, P, sl, b);
-        SeedArgs sd = seedArgs(c, P, sl, b);
+        const RoundEv ev = eventsOf(sl, r);
+        const uint32_t nitems = (uint32_t)((bstart[b + 1] - bstart[b]) * c->rounds[r].nsearch);
+        if (r == 0) {
+            reserveSlot(c, sl);
+            SH_HIP(hipStreamWaitEvent(sA, sl.free, 0));  // the slot's previous batch is fully consumed
+            const uint32_t most = (uint32_t)((bstart[b + 1] - bstart[b]) * c->nsearch);  // of any round
+            sl.seeds.reserve(most);
+            sl.seedItem.reserve(most);
+        }
+        const SearchArgs a = searchArgs(c, P, sl, b, r);
+        SeedArgs sd = seedArgs(c, P, sl, b, r);
         // seeds on their own stream (sD), so that they run ahead of the FM
         // phase of the batch before (both are HBM-latency bound and light)
-        SH_HIP(hipStreamWaitEvent(sD, sl.free, 0));
+        if (r == 0) {
+            SH_HIP(hipStreamWaitEvent(sD, sl.free, 0));
+        } else {
+            SH_HIP(hipStreamWaitEvent(sD, eventsOf(sl, r - 1).textDone, 0));
+            launchRoundReset(sl.small.ptr, sl.queues.ptr, sD);
+        }
         // streamed upload: the batch's patterns (packed here on the host while
         // the batches before it search; unpacked on sD ahead of its seeds)
         auto seeds = [&](uint32_t i0, uint32_t i1) {
@@ -416,7 +464,7 @@ struct Pass {
         } else {
             sl.seedsInParts = false;
             ensureUploaded(c, bstart[b + 1], sD);
-            SH_HIP(hipEventRecord(sl.fmStart, sD));
+            SH_HIP(hipEventRecord(ev.fmStart, sD));
             seeds(0, nitems);
             // the seed tasks end here: the text phase may start on them (a
             // lone device-resident batch's text phase waits for its FM phase:
@@ -424,25 +472,34 @@ struct Pass {
             if (P.split && P.early) seedTasksDone(sl);
             SH_HIP(hipEventRecord(sl.seedDone0, sD));
         }
-        SH_HIP(hipEventRecord(sl.seedDone, sD));
-        SH_HIP(hipStreamWaitEvent(sA, sl.seedDone, 0));
-        SH_HIP(hipEventRecord(sl.fmBegin, sA));
+        SH_HIP(hipEventRecord(ev.seedDone, sD));
+        SH_HIP(hipStreamWaitEvent(sA, ev.seedDone, 0));
+        SH_HIP(hipEventRecord(ev.fmBegin, sA));
         launchSearch(a, c->I.sigma, c->edit, P.count, b == 0 && !P.early ? P.firstBlocks : P.blocks, P.fmLds, sA);
-        SH_HIP(hipEventRecord(sl.fmDone, sA));
+        SH_HIP(hipEventRecord(ev.fmDone, sA));
         ++S.search_launches;
+    }
+
+    // every round of batch b in turn
+    void issueRounds(uint64_t b) {
+        for (uint32_t r = 0; r < P.rounds; ++r) {
+            issueFM(b, r);
+            issueText(b, r);
+        }
     }
 
     // one launch per batch (kSearchTextBatch) after its FM phase; the
     // first batch of an early pass in two: its seed tasks while its FM
     // phase runs, then the tasks the FM phase appended after them
-    void issueText(uint64_t b) {
+    void issueText(uint64_t b, uint32_t r) {
         Ctx::Slot& sl = slotOf(b);
-        const bool split0 = P.early && b == 0;
+        const RoundEv ev = eventsOf(sl, r);
+        const bool split0 = P.early && b == 0;  // (one round: ev is the slot's own events)
         sl.twoText = P.split && split0;
-        SH_HIP(hipStreamWaitEvent(sB, split0 ? sl.seedDone0 : sl.fmDone, 0));
-        SH_HIP(hipEventRecord(sl.textStart, sB));
+        SH_HIP(hipStreamWaitEvent(sB, split0 ? sl.seedDone0 : ev.fmDone, 0));
+        SH_HIP(hipEventRecord(ev.textStart, sB));
         if (P.split) {
-            TextBatchArgs t = textArgs(c, P, sl, b);
+            TextBatchArgs t = textArgs(c, P, sl, b, r);
             if (split0) {
                 t.taskCount = sl.small.ptr + kSwSeedTasks;
                 launchTextBatch(t, c->I.sigma, c->edit, P.count, P.textBlocks, P.tx.lds, sB);
@@ -457,12 +514,21 @@ struct Pass {
             launchTextBatch(t, c->I.sigma, c->edit, P.count, P.textBlocks, P.tx.lds, sB);
             ++S.text_launches;
         }
-        SH_HIP(hipEventRecord(sl.textDone, sB));
+        SH_HIP(hipEventRecord(ev.textDone, sB));
     }
 
-    // the batch's kernel spans (Slot's events) into the stats
-    void addSpans(const Ctx::Slot& sl) {
+    // the batch's kernel spans (Slot's events) into the stats, summed over its rounds
+    void addSpans(Ctx::Slot& sl) {
         float ms = 0;
+        for (uint32_t r = 0; r + 1 < P.rounds; ++r) {
+            const RoundEv ev = eventsOf(sl, r);
+            SH_HIP(hipEventElapsedTime(&ms, ev.fmStart, ev.seedDone));
+            S.seed_ms += ms;
+            SH_HIP(hipEventElapsedTime(&ms, ev.fmBegin, ev.fmDone));
+            S.search_ms += ms;
+            SH_HIP(hipEventElapsedTime(&ms, ev.textStart, ev.textDone));
+            S.text_ms += ms;
+        }
         if (sl.seedsInParts) {  // the seed launches, not the upload waits between them
             SH_HIP(hipEventElapsedTime(&ms, sl.fmStart, sl.seedDone0));
             for (uint32_t i = 0; i < sl.seedParts; ++i) {
@@ -677,7 +743,7 @@ static void readCounters(Ctx* c, const PassPlan& P, sahara_stats& S, hipStream_t
         {&sahara_stats::text_cycles_refill, kCtCyRefill}, {&sahara_stats::text_cycles_step, kCtCyStep},
         {&sahara_stats::text_cycles_emit, kCtCyEmit}, {&sahara_stats::text_compare_steps, kCtCompareSteps},
         {&sahara_stats::text_steps, kCtTextSteps}, {&sahara_stats::text_pos_tasks, kCtPosTasks},
-        {&sahara_stats::text_stolen, kCtStolen}};
+        {&sahara_stats::text_stolen, kCtStolen}, {&sahara_stats::best_skipped, kCtBestSkipped}};
     for (const auto& so : statOf) S.*so.first = h[so.second];
     if (P.k.dump) {
         for (uint32_t i = 0; i < kCounters; ++i) std::fprintf(stderr, "%s%llu", i ? " " : "counters ", h[i]);
@@ -707,6 +773,7 @@ void runPass(Ctx* c, bool count, bool redo, sahara_stats& S, bool& overflow) {
     S.search_grid = P.blocks;
     S.text_grid = P.split ? P.textBlocks : 0u;
     S.pipelined = P.serial ? 0u : 1u;
+    S.best_rounds = P.rounds > 1 ? P.rounds : 0u;
     c->stack.reserve((size_t)P.stackLevels * std::max(P.blocks, P.firstBlocks) * 256);  // levels beyond the LDS part
     initWorkCaps(c, P.maxBatch, P.k);
     // Pinned, so that the records' copies are plain DMA writes: a copy into
@@ -742,6 +809,8 @@ void runPass(Ctx* c, bool count, bool redo, sahara_stats& S, bool& overflow) {
     c->outStale = false;
     SH_HIP(hipMemsetAsync(c->small.ptr, 0, 8 * sizeof(uint32_t), ps.sC));  // the locate chain's words (finish)
     for (auto& sl : c->slot) ps.resetSlot(sl, ps.sA);
+    for (auto& sl : c->slot)  // the earlier rounds' events (Pass::eventsOf), before the pass's threads start
+        while (sl.earlier.size() + 1 < P.rounds) sl.earlier.emplace_back();
 
     if (!P.serial) {
         // Two host threads (host_pool.h issueAndFinish). This one packs the
@@ -759,8 +828,7 @@ void runPass(Ctx* c, bool count, bool redo, sahara_stats& S, bool& overflow) {
         };
         auto issue = [&](uint64_t b) {
             c->mark("issue", b);
-            ps.issueFM(b);
-            ps.issueText(b);
+            ps.issueRounds(b);
             c->mark("issued", b);
             ++S.batches;
         };
@@ -785,8 +853,7 @@ void runPass(Ctx* c, bool count, bool redo, sahara_stats& S, bool& overflow) {
             ++S.batches;
             for (;;) {  // re-run the batch until its buffers suffice
                 overflow = false;
-                ps.issueFM(b);
-                ps.issueText(b);
+                ps.issueRounds(b);
                 if (ps.finish(b)) {
                     ps.finishCheck(b);
                     break;

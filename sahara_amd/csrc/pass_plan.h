@@ -172,6 +172,24 @@ inline TextGeometry textGeometry(uint32_t m, uint32_t maxErr, uint32_t patBlocks
     return g;
 }
 
+// The one geometry of a pass of several rounds: every round runs with the
+// FM LDS and stack, the text geometry and the batch size of the worst round,
+// i.e. of the most searches and the most errors of any round (a round with
+// fewer of either uses a prefix of the tables' LDS, a shorter stack and a
+// window that is wider than it needs).
+struct WorstRound {
+    uint32_t nsearch = 0, maxErr = 0;
+};
+template <typename Rounds>
+inline WorstRound worstRound(const Rounds& rounds) {
+    WorstRound w;
+    for (const auto& r : rounds) {
+        w.nsearch = std::max(w.nsearch, r.nsearch);
+        w.maxErr = std::max(w.maxErr, r.maxErr);
+    }
+    return w;
+}
+
 // Everything a pass fixes before its first HIP call (pass.cpp makePlan);
 // the stages read it and nothing else decides
 struct PassPlan {
@@ -189,6 +207,10 @@ struct PassPlan {
     // chunk by chunk as the upload arrives (chunked0); the finisher sleeps in
     // its waits; (count mode, k.dump) the first text launch's wave lives
     bool early = false, chunked0 = false, sleepy = false, probe = false;
+    // rounds per batch (besthits: one per exact-j scheme, else 1). The
+    // geometry above is planned once, for the worst round: the most searches,
+    // the most errors, the largest tables (worstRound).
+    uint32_t rounds = 1;
     uint64_t nbatch() const { return bstart.size() - 1; }
 };
 

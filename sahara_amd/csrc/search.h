@@ -71,6 +71,11 @@ struct SeedArgs {
     uint32_t* taskCount;
     uint32_t* flags;            // kFlagTasks: task buffer too small
     unsigned long long* counters;  // count mode: text tasks (kCtTextTasks), else nullptr
+    // besthits rounds (pass.cpp): the batch's per-pattern row counts so far
+    // (the slot's qcnt), nullptr = none. An item whose pattern has reported
+    // (skip[pid] != 0) is dropped before its k-mer lookup: no seed, no task;
+    // count mode counts the dropped items (kCtBestSkipped).
+    const uint32_t* skip;
 };
 
 // Layouts that the host code (pass.cpp) and the kernels share, each defined
@@ -78,6 +83,7 @@ struct SeedArgs {
 // the words of a slot's counters (Ctx::Slot::small); kBatchTotals copies all
 // kSlotWords of them into the batch's record
 enum SlotWord : uint32_t {
+    kSwRoundTasks = 0,  // taskCount when the round began (kRoundReset): the round's text launch starts there
     kSwHitCount = 1, kSwFlags = 2, kSwFilled = 3, kSwTaskCount = 4,
     kSwSeedTasks = 5,  // taskCount once the batch's seed tasks are all written (an early text launch's end)
     kSwSeedCount = 6, kSlotWords = 8
@@ -119,6 +125,7 @@ enum Counter : uint32_t {
     kCtCyRefill = 11, kCtCyStep = 12, kCtCyEmit = 13,  // text-kernel cycles
     kCtCompareSteps = 14, kCtTextSteps = 15,
     kCtPosTasks = 16,  // text tasks that came with their text position (kTaskPos)
+    kCtBestSkipped = 17,  // items of patterns that had reported in an earlier round (SeedArgs::skip)
     // TextBatchArgs::probe, the pass's first text launch, wall clock (10 ns):
     // per wave that saw the queue dry, its time after that and their number
     kCtDryRun = 30, kCtDryWaves = 31,
@@ -192,6 +199,12 @@ int textShapeOf(uint32_t winBlocks, uint32_t patBlocks, bool exactWindow);
 void launchTextBatch(const TextBatchArgs& a, uint32_t sigma, bool edit, bool count, uint32_t blocks, size_t lds,
                      hipStream_t st);
 void launchSeeds(const SeedArgs& a, uint32_t sigma, uint32_t blocks, hipStream_t st);
+// Between two rounds of a batch (besthits, pass.cpp): what a round consumes in
+// the slot is reset: the seed count and the queue words are zero afterwards,
+// and kSwRoundTasks holds the task count so far, where the next round's text
+// launch begins. The hit count, filled, the flags, the task count (and qcnt,
+// rank) carry over.
+void launchRoundReset(uint32_t* small, uint32_t* queues, hipStream_t st);
 void launchPackPatterns(const uint8_t* src, uint64_t npat, uint32_t m, uint32_t patWords, uint32_t sigma,
                         uint32_t* dst, uint32_t* bad, hipStream_t st);
 // n symbols, two per byte of nib (low nibble first) -> one per byte of dst

@@ -286,9 +286,14 @@ __device__ __forceinline__ uint32_t seedCode(const SeedArgs& a, uint32_t i) {
 // translation, not bandwidth, bounds these random lookups: tools/gather_bench).
 // Must be called by all lanes of the wave.
 template <int SIGMA>
-__device__ __forceinline__ uint4 seedOf(const SeedArgs& a, uint32_t i, bool& keep, uint32_t& textPos) {
+__device__ __forceinline__ uint4 seedOf(const SeedArgs& a, uint32_t i, bool& keep, uint32_t& textPos,
+                                        bool& skipped) {
     keep = i < a.nitems;
-    const uint32_t code = seedCode<SIGMA>(a, i);
+    // besthits: the pattern reported in an earlier round (nothing writes the
+    // counts while the seeds run: pass.cpp issueFM)
+    skipped = keep && a.skip && a.skip[i / a.nsearch] != 0u;
+    keep = keep && !skipped;
+    const uint32_t code = keep ? seedCode<SIGMA>(a, i) : ~0u;
     const bool need = keep && code != ~0u;
     const bool odd = (threadIdx.x & 1u) != 0u;
     const uint64_t own = (uint64_t)(a.kmer + (need ? code : 0u));
@@ -319,14 +324,16 @@ __global__ __launch_bounds__(256) void kSeedItems(SeedArgs a) {
     __shared__ uint32_t wcount[2][4], blockBase[2];
     const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
     const uint64_t ltMask = (1ull << lane) - 1ull;
-    uint64_t cTasks = 0;
+    uint64_t cTasks = 0, cSkipped = 0;
     for (uint32_t base = a.itemBegin + blockIdx.x * 1024u; base < a.nitems; base += gridDim.x * 1024u) {  // block-uniform
         uint4 cur[4];
         uint32_t tpos[4];
         bool keep[4], task[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            cur[k] = seedOf<SIGMA>(a, base + k * 256u + threadIdx.x, keep[k], tpos[k]);
+            bool skipped;
+            cur[k] = seedOf<SIGMA>(a, base + k * 256u + threadIdx.x, keep[k], tpos[k], skipped);
+            cSkipped += skipped ? 1u : 0u;
             task[k] = keep[k] && a.toText && cur[k].z == 1u && (cur[k].w & 0xFFFFu) < a.m;
             keep[k] = keep[k] && !task[k];
         }
@@ -378,6 +385,7 @@ __global__ __launch_bounds__(256) void kSeedItems(SeedArgs a) {
         atomicAdd(a.counters + kCtTextTasks, (unsigned long long)cTasks);
         if (a.kmerPos) atomicAdd(a.counters + kCtPosTasks, (unsigned long long)cTasks);
     }
+    if (a.counters && cSkipped) atomicAdd(a.counters + kCtBestSkipped, (unsigned long long)cSkipped);
 }
 
 // =========================================================== phase 1: FM ====
@@ -2233,6 +2241,19 @@ __global__ void kBatchTotals(uint32_t* __restrict__ small, uint32_t* __restrict_
         segCounts[i - 10] = 0;
     }
     for (uint32_t w = i; w < kQueuesWords; w += blockDim.x) queues[w] = 0;
+}
+
+__global__ void kRoundReset(uint32_t* __restrict__ small, uint32_t* __restrict__ queues) {
+    if (threadIdx.x == 0) {
+        small[kSwRoundTasks] = small[kSwTaskCount];
+        small[kSwSeedCount] = 0;
+    }
+    for (uint32_t w = threadIdx.x; w < kQueuesWords; w += blockDim.x) queues[w] = 0;
+}
+
+void launchRoundReset(uint32_t* small, uint32_t* queues, hipStream_t st) {
+    hipLaunchKernelGGL(kRoundReset, dim3(1), dim3(256), 0, st, small, queues);
+    SH_HIP(hipGetLastError());
 }
 
 void launchBatchTotals(uint32_t* small, uint32_t* queues, const uint64_t* rowTotal, uint32_t* segCounts, uint32_t* out,

@@ -635,34 +635,60 @@ void ensureUploaded(Ctx* c, uint64_t patEnd, hipStream_t kst) {
 }
 
 // The scheme half of staging: host tables, their upload, the k-mer starts.
-void stageScheme(Ctx* c, uint64_t npat, uint32_t m, const uint32_t* pi, const uint32_t* l, const uint32_t* u,
-                 uint32_t ns, int edit) {
+// Several schemes (the rounds of a besthits call) lie side by side in the
+// same three device arrays (Ctx::rounds).
+void stageSchemes(Ctx* c, uint64_t npat, uint32_t m, const uint32_t* pi, const uint32_t* l, const uint32_t* u,
+                  const uint32_t* ns, uint32_t nrounds, int edit) {
     if (npat == 0) throw Error("no patterns");
-    std::vector<uint32_t> packed, cover;
-    packSchemeTable(pi, l, u, ns, m, packed, c->maxErr);
-    if ((size_t)ns * m * 4 > 60 * 1024) throw Error("scheme too large for LDS (searches * len > 15360)");
-    if (ns > 255) throw Error("at most 255 searches per scheme");
-    textTable(pi, l, u, ns, m, packed, cover);
-    c->scheme.reserve(packed.size());
-    SH_HIP(hipMemcpyAsync(c->scheme.ptr, packed.data(), packed.size() * 4, hipMemcpyHostToDevice, c->st));
-    c->cover.reserve(cover.size());
-    SH_HIP(hipMemcpyAsync(c->cover.ptr, cover.data(), cover.size() * 4, hipMemcpyHostToDevice, c->st));
-    // searches whose first kmerK steps admit no error start from the k-mer table
-    std::vector<uint32_t> kst(ns, 0xFFFFFFFFu);
+    if (nrounds == 0) throw Error("no search scheme");
+    std::vector<uint32_t> packedAll, coverAll, kstAll;
+    std::vector<Ctx::Round> rounds;
+    uint32_t nsMax = 0, errMax = 0;
     const uint32_t K = c->I.kmerK;
-    for (uint32_t s = 0; K && K <= m && s < ns; ++s) {
-        bool exact = true;
-        uint32_t lo = pi[(size_t)s * m];
-        for (uint32_t p = 0; p < K; ++p) {
-            exact = exact && u[(size_t)s * m + p] == 0;
-            lo = std::min(lo, pi[(size_t)s * m + p]);
+    for (uint32_t r = 0; r < nrounds; ++r) {
+        const uint32_t n = ns[r];
+        std::vector<uint32_t> packed, cover;
+        Ctx::Round R;
+        packSchemeTable(pi, l, u, n, m, packed, R.maxErr);
+        if ((size_t)n * m * 4 > 60 * 1024) throw Error("scheme too large for LDS (searches * len > 15360)");
+        if (n > 255) throw Error("at most 255 searches per scheme");
+        textTable(pi, l, u, n, m, packed, cover);
+        R.nsearch = n;
+        R.schemeAt = packedAll.size();
+        R.coverAt = coverAll.size();  // (even: the text kernel reads the table as uint2)
+        R.kmerAt = kstAll.size();
+        packedAll.insert(packedAll.end(), packed.begin(), packed.end());
+        coverAll.insert(coverAll.end(), cover.begin(), cover.end());
+        if (coverAll.size() & 1u) coverAll.push_back(0);
+        // searches whose first kmerK steps admit no error start from the k-mer table
+        std::vector<uint32_t> kst(n, 0xFFFFFFFFu);
+        for (uint32_t s = 0; K && K <= m && s < n; ++s) {
+            bool exact = true;
+            uint32_t lo = pi[(size_t)s * m];
+            for (uint32_t p = 0; p < K; ++p) {
+                exact = exact && u[(size_t)s * m + p] == 0;
+                lo = std::min(lo, pi[(size_t)s * m + p]);
+            }
+            if (exact) kst[s] = lo;
         }
-        if (exact) kst[s] = lo;
+        kstAll.insert(kstAll.end(), kst.begin(), kst.end());
+        rounds.push_back(R);
+        nsMax = std::max(nsMax, n);
+        errMax = std::max(errMax, R.maxErr);
+        pi += (size_t)n * m;
+        l += (size_t)n * m;
+        u += (size_t)n * m;
     }
-    c->kmerStart.reserve(ns);
-    SH_HIP(hipMemcpyAsync(c->kmerStart.ptr, kst.data(), ns * 4, hipMemcpyHostToDevice, c->st));
+    c->scheme.reserve(packedAll.size());
+    SH_HIP(hipMemcpyAsync(c->scheme.ptr, packedAll.data(), packedAll.size() * 4, hipMemcpyHostToDevice, c->st));
+    c->cover.reserve(coverAll.size());
+    SH_HIP(hipMemcpyAsync(c->cover.ptr, coverAll.data(), coverAll.size() * 4, hipMemcpyHostToDevice, c->st));
+    c->kmerStart.reserve(kstAll.size());
+    SH_HIP(hipMemcpyAsync(c->kmerStart.ptr, kstAll.data(), kstAll.size() * 4, hipMemcpyHostToDevice, c->st));
     SH_HIP(hipStreamSynchronize(c->st));
-    c->nsearch = ns;
+    c->rounds = std::move(rounds);
+    c->nsearch = nsMax;
+    c->maxErr = errMax;
     c->edit = edit != 0;
 }
 
@@ -731,12 +757,12 @@ static void stagePackedN(Ctx* c, const PackedReads& P, uint64_t rows, uint32_t m
 // one rank per byte, or (packed) two bits per symbol with the N positions
 // listed (the reads of sahara_gpu_search_packed[_compact]).
 void stageStreamed(Ctx* c, const uint8_t* src, uint64_t rows, bool rc, uint64_t npat, uint32_t m,
-                   const uint32_t* pi, const uint32_t* l, const uint32_t* u, uint32_t ns, int edit,
-                   const PackedReads* packed) {
+                   const uint32_t* pi, const uint32_t* l, const uint32_t* u, const uint32_t* ns, uint32_t nrounds,
+                   int edit, const PackedReads* packed) {
     c->sk = {};  // a new call
     if (m == 0 || m > kMaxPatternLen) throw Error("pattern length out of range");
     if (packed && c->I.sigma != 5 && c->I.sigma != 6) throw Error("reads two bits per symbol need a dna4 or dna5 index");
-    stageScheme(c, npat, m, pi, l, u, ns, edit);
+    stageSchemes(c, npat, m, pi, l, u, ns, nrounds, edit);
     c->m = m;
     c->npat = npat;
     c->patWords = (m + 7) / 8;
@@ -792,13 +818,17 @@ void stageStreamed(Ctx* c, const uint8_t* src, uint64_t rows, bool rc, uint64_t 
 }
 
 void stage(Ctx* c, const uint8_t* ranks, uint64_t npat, uint32_t m, const uint32_t* pi, const uint32_t* l,
-           const uint32_t* u, uint32_t ns, int edit) {
+           const uint32_t* u, const uint32_t* ns, uint32_t nrounds, int edit) {
     if (npat == 0) throw Error("no patterns");
+    if (nrounds == 0) throw Error("no search scheme");
     c->sk = {};  // a new call
-    std::vector<uint32_t> packed;
-    packSchemeTable(pi, l, u, ns, m, packed, c->maxErr);  // a bad scheme fails before the upload
-    if ((size_t)ns * m * 4 > 60 * 1024) throw Error("scheme too large for LDS (searches * len > 15360)");
-    if (ns > 255) throw Error("at most 255 searches per scheme");
+    for (size_t r = 0, at = 0; r < nrounds; at += (size_t)ns[r] * m, ++r) {  // a bad scheme fails before the upload
+        std::vector<uint32_t> packed;
+        uint32_t maxErr = 0;
+        packSchemeTable(pi + at, l + at, u + at, ns[r], m, packed, maxErr);
+        if ((size_t)ns[r] * m * 4 > 60 * 1024) throw Error("scheme too large for LDS (searches * len > 15360)");
+        if (ns[r] > 255) throw Error("at most 255 searches per scheme");
+    }
     const auto t0 = std::chrono::steady_clock::now();
     c->patWords = (m + 7) / 8;
     {
@@ -816,7 +846,7 @@ void stage(Ctx* c, const uint8_t* ranks, uint64_t npat, uint32_t m, const uint32
         SH_HIP(hipStreamSynchronize(c->st));
         if (bad) throw Error("pattern rank out of range for this index");
     }
-    stageScheme(c, npat, m, pi, l, u, ns, edit);
+    stageSchemes(c, npat, m, pi, l, u, ns, nrounds, edit);
     c->npat = npat;
     c->m = m;
     c->sk.staged = true;
