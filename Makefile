@@ -17,7 +17,7 @@ BUILD_ID := $(shell python3 tools/build_id.py)
 $(shell mkdir -p $(OBJDIR) && echo '#define SAHARA_BUILD_ID "$(BUILD_ID)"' > $(OBJDIR)/build_id.h.new && \
         (cmp -s $(OBJDIR)/build_id.h.new $(OBJDIR)/build_id.h || mv $(OBJDIR)/build_id.h.new $(OBJDIR)/build_id.h))
 
-OBJS := $(OBJDIR)/index_build.o $(OBJDIR)/search.o $(OBJDIR)/capi.o $(OBJDIR)/staging.o $(OBJDIR)/pass.o \
+OBJS := $(OBJDIR)/index_build.o $(OBJDIR)/search.o $(OBJDIR)/align.o $(OBJDIR)/capi.o $(OBJDIR)/staging.o $(OBJDIR)/pass.o \
         $(OBJDIR)/host_util.o $(OBJDIR)/scheme.o
 
 all: $(LIB) oracle $(if $(wildcard sahara_amd/cli/*.cpp),$(CLI),) tools/gather_bench
@@ -53,7 +53,7 @@ oracle:
 # test suite against them.
 ASAN_HOST := -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined -Xarch_host -fno-omit-frame-pointer
 ASANDIR   := build/asan
-ASAN_OBJS := $(ASANDIR)/index_build.o $(ASANDIR)/search.o $(ASANDIR)/capi.o $(ASANDIR)/staging.o $(ASANDIR)/pass.o \
+ASAN_OBJS := $(ASANDIR)/index_build.o $(ASANDIR)/search.o $(ASANDIR)/align.o $(ASANDIR)/capi.o $(ASANDIR)/staging.o $(ASANDIR)/pass.o \
              $(ASANDIR)/host_util.o $(ASANDIR)/scheme.o
 
 $(ASANDIR)/%.o: $(CSRC)/%.hip $(HDRS)

@@ -256,6 +256,53 @@ int  sahara_gpu_search_best_packed_compact(void* ctx, const uint8_t* codes, uint
                                            uint64_t limit, const uint32_t* pi, const uint32_t* l, const uint32_t* u,
                                            const uint32_t* n_searches, uint32_t n_schemes, sahara_hit_blocks* out);
 
+/* --- alignment of located hits (docs/semantics.md "Alignments") ---
+ * A hit says where a pattern occurs and, at most, with how many errors. These
+ * calls turn hits into alignments on the device: per hit the least number of
+ * edits e* between the pattern and the text at the hit's position, the
+ * number of text symbols the alignment covers and the edits themselves.
+ * e* depends on the pattern and the position only: duplicate hits at one
+ * position get the same record, whose err is e*, not the hit's own err.
+ * A position where the pattern does not align within max_err gives
+ * err = SAHARA_ALIGN_NONE, ref_len = 0 and no edits. */
+#define SAHARA_ALIGN_MAX_ERR 8
+#define SAHARA_ALIGN_NONE 0xFFFFFFFFu
+typedef struct sahara_alignment {      /* 24 B */
+    uint32_t err;      /* e*, or SAHARA_ALIGN_NONE */
+    uint32_t ref_len;  /* text symbols covered: len - #I + #D */
+    uint16_t edit[SAHARA_ALIGN_MAX_ERR]; /* err entries in pattern order: qpos << 2 | kind,
+                                            kind 1 X, 2 I, 3 D; qpos = pattern symbols before the edit; rest 0 */
+} sahara_alignment;
+/* ranks: the patterns exactly as sahara_gpu_search took them (qid i = pattern
+ * i); hits in any order; out: the caller's n_hits records, record i for hit
+ * i. edit == 0: substitutions only (-d ham). Refused with a negative code
+ * before anything is aligned or written: max_err > SAHARA_ALIGN_MAX_ERR,
+ * len == 0 or len > 16383, a hit whose qid, seq_id or pos names no pattern,
+ * record or position of its record. Hits go up and records come down in
+ * chunks (SAHARA_ALIGN_CHUNK hits, a test hook). A multi-part index aligns
+ * each hit against the part that holds its record. */
+int  sahara_gpu_align(void* ctx, const uint8_t* ranks, uint64_t n_patterns, uint32_t len, int edit, uint32_t max_err,
+                      const sahara_hit* hits, uint64_t n_hits, sahara_alignment* out);
+/* The same for the compact records of sahara_gpu_search_packed_compact (or
+ * its besthits twin) over the same reads: codes, sym0, n_pos, n_count,
+ * n_reads, len, reverse and limit as that call took them, so the qids agree;
+ * out: blocks->n_hits records, record i for blocks->recs[i]. Needs a
+ * single-part index, as its search twin. */
+int  sahara_gpu_align_packed_compact(void* ctx, const uint8_t* codes, uint64_t sym0, const uint64_t* n_pos,
+                                     uint64_t n_count, uint64_t n_reads, uint32_t len, int reverse, uint64_t limit,
+                                     int edit, uint32_t max_err, const sahara_hit_blocks* blocks, sahara_alignment* out);
+/* Figures of the context's last alignment call. */
+typedef struct sahara_align_stats {
+    uint64_t hits;       /* records written */
+    uint64_t chunks;     /* chunks they went through */
+    double   kernel_ms;  /* device time of the alignment kernel (HIP events) */
+    double   stage_ms;   /* wall time of staging the patterns */
+    double   total_ms;   /* wall time of the whole call */
+} sahara_align_stats;
+int  sahara_gpu_align_stats(void* ctx, sahara_align_stats* stats);
+/* host only, no context: the extended CIGAR ("57=1X42=") of one record; returns its length, -1 if cap is too small or the record is NONE */
+int  sahara_cigar(const sahara_alignment* a, uint32_t len, char* buf, size_t cap);
+
 /* Device-resident form of the same path for benchmarking: stage patterns and
  * scheme once, run search+locate+sort with results left in HBM, fetch later. */
 int  sahara_gpu_stage(void* ctx, const uint8_t* ranks, uint64_t n_patterns, uint32_t len,

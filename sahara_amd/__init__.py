@@ -22,7 +22,8 @@ import numpy as np
 __all__ = [
     "BiFMIndex", "HIT_DTYPE", "search", "search_reads", "search_reads_compact", "CompactHits", "PackedReads",
     "pack_reads", "search_packed", "search_packed_compact", "search_best", "search_best_reads", "search_best_packed",
-    "search_best_packed_compact", "read_fasta", "search_scheme", "scheme_parts",
+    "search_best_packed_compact", "ALIGN_DTYPE", "ALIGN_MAX_ERR", "ALIGN_NONE", "align", "align_packed_compact",
+    "align_stats", "cigar", "read_fasta", "search_scheme", "scheme_parts",
     "scheme_generators",
     "scheme_counts", "synth_reference", "synth_reads", "interleave_rc", "load_fasta",
     "library_path", "lib", "SaharaError", "DNA5", "DNA4",
@@ -36,6 +37,10 @@ DNA5 = {"sigma": 6, "chars": "$ACGNT"}
 DNA4 = {"sigma": 5, "chars": "$ACGT"}
 
 HIT_DTYPE = np.dtype([("qid", "<u8"), ("seq_id", "<u4"), ("err", "<u4"), ("pos", "<u8")])
+# sahara_alignment (include/sahara_hip.h): one record per aligned hit
+ALIGN_MAX_ERR = 8
+ALIGN_NONE = 0xFFFFFFFF
+ALIGN_DTYPE = np.dtype([("err", "<u4"), ("ref_len", "<u4"), ("edit", "<u2", (ALIGN_MAX_ERR,))])
 
 u8p = C.POINTER(C.c_uint8)
 u32p = C.POINTER(C.c_uint32)
@@ -87,6 +92,11 @@ class Stats(C.Structure):
                 ((n, getattr(self, n)) for n, _ in self._fields_)}
 
 
+class AlignStats(C.Structure):
+    _fields_ = [("hits", C.c_uint64), ("chunks", C.c_uint64), ("kernel_ms", C.c_double), ("stage_ms", C.c_double),
+                ("total_ms", C.c_double)]
+
+
 EXPORTED = {
     # name: (restype, argtypes)
     "sahara_gpu_last_error": (C.c_char_p, []),
@@ -136,6 +146,13 @@ EXPORTED = {
     "sahara_gpu_search_best_packed_compact": (C.c_int, [C.c_void_p, u8p, C.c_uint64, u64p, C.c_uint64, C.c_uint64,
                                                         C.c_uint32, C.c_int, C.c_uint64, u32p, u32p, u32p, u32p,
                                                         C.c_uint32, C.POINTER(HitBlocks)]),
+    "sahara_gpu_align": (C.c_int, [C.c_void_p, u8p, C.c_uint64, C.c_uint32, C.c_int, C.c_uint32, C.c_void_p,
+                                   C.c_uint64, C.c_void_p]),
+    "sahara_gpu_align_packed_compact": (C.c_int, [C.c_void_p, u8p, C.c_uint64, u64p, C.c_uint64, C.c_uint64,
+                                                  C.c_uint32, C.c_int, C.c_uint64, C.c_int, C.c_uint32,
+                                                  C.POINTER(HitBlocks), C.c_void_p]),
+    "sahara_gpu_align_stats": (C.c_int, [C.c_void_p, C.POINTER(AlignStats)]),
+    "sahara_cigar": (C.c_int, [C.c_void_p, C.c_uint32, C.c_char_p, C.c_size_t]),
     "sahara_gpu_stage": (C.c_int, [C.c_void_p, u8p, C.c_uint64, C.c_uint32, u32p, u32p, u32p,
                                    C.c_uint32, C.c_int]),
     "sahara_gpu_run": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]),
@@ -604,6 +621,55 @@ def search_packed_compact(index, packed, scheme, edit=True, reverse=True, limit=
     _check(lib().sahara_gpu_search_packed_compact(index._h, *a, int(reverse), int(limit), _p(pi, u32p), _p(l, u32p),
                                                   _p(u, u32p), pi.shape[0], int(edit), C.byref(b)))
     return CompactHits(b, index)
+
+
+def align(index, queries, hits, edit=True, max_err=ALIGN_MAX_ERR):
+    """Alignments of located hits (sahara_gpu_align; docs/semantics.md
+    "Alignments"): queries as search() took them, hits a HIT_DTYPE array in
+    any order. Returns an ALIGN_DTYPE array, record i for hit i: err = the
+    least number of edits at the hit's position (ALIGN_NONE: more than
+    max_err), ref_len, and the edits as qpos << 2 | kind (1 X, 2 I, 3 D)."""
+    q = np.ascontiguousarray(queries, dtype=np.uint8)
+    if q.ndim != 2 or q.shape[0] == 0:
+        raise SaharaError("queries must be a non-empty (n_patterns, len) array")
+    h = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    out = np.zeros(len(h), ALIGN_DTYPE)
+    _check(lib().sahara_gpu_align(index._h, _p(q, u8p), q.shape[0], q.shape[1], int(edit), int(max_err),
+                                  h.ctypes.data_as(C.c_void_p), len(h), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def align_packed_compact(index, packed, compact_hits, edit=True, reverse=True, limit=0, max_err=ALIGN_MAX_ERR):
+    """align() for the records of search_packed_compact (or its besthits twin)
+    over the same PackedReads, reverse and limit
+    (sahara_gpu_align_packed_compact): record i for compact_hits.recs[i]."""
+    if packed.n_reads <= 0:
+        raise SaharaError("no reads")
+    if compact_hits._b is None:
+        raise SaharaError("the compact hits are closed")
+    out = np.zeros(len(compact_hits), ALIGN_DTYPE)
+    _check(lib().sahara_gpu_align_packed_compact(
+        index._h, _p(packed.codes, u8p), packed.sym0, _p(packed.n_pos, u64p) if packed.n_pos.size else None,
+        packed.n_pos.size, packed.n_reads, packed.length, int(reverse), int(limit), int(edit), int(max_err),
+        C.byref(compact_hits._b), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def align_stats(index):
+    """Figures of the index's last align call (sahara_gpu_align_stats)."""
+    s = AlignStats()
+    _check(lib().sahara_gpu_align_stats(index._h, C.byref(s)))
+    return {n: getattr(s, n) for n, _ in s._fields_}
+
+
+def cigar(record, length):
+    """Extended CIGAR ("57=1X42=") of one ALIGN_DTYPE record of a pattern of
+    `length` symbols (sahara_cigar); None for an ALIGN_NONE record."""
+    r = np.ascontiguousarray(record, dtype=ALIGN_DTYPE).reshape(1)
+    cap = 16 * (ALIGN_MAX_ERR + 2)
+    buf = C.create_string_buffer(cap)
+    n = lib().sahara_cigar(r.ctypes.data_as(C.c_void_p), int(length), buf, cap)
+    return buf.raw[:n].decode() if n >= 0 else None
 
 
 def read_fasta(path, sigma=6, form=1, threads=0):

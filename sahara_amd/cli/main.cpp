@@ -206,6 +206,7 @@ struct HitPart {
     bool compact = false;
     uint64_t n = 0;
     uint64_t qidOffset = 0;
+    std::vector<sahara_alignment> aln;  // --emit-cigar: record i of hit i, aligned by the hit's own device
     void release() {
         if (compact) sahara_gpu_free_blocks(&blocks);
         else sahara_gpu_free(hits);
@@ -214,7 +215,8 @@ struct HitPart {
     }
 };
 
-// Text output of hits: "qid seqId pos[ e]\n" (search.cpp:254-261). Blocks of
+// Text output of hits: "qid seqId pos[ e][ cigar]\n" (search.cpp:254-261; the
+// CIGAR of patterns of cigarLen symbols when the parts carry alignments). Blocks of
 // hits are formatted by nt threads, each taking the next block in order; a
 // block's file offset is the previous block's end, published as soon as that
 // block is formatted, so each thread writes its own block (pwrite) while the
@@ -222,7 +224,8 @@ struct HitPart {
 // Compact records are decoded right here, in the formatting loop that runs
 // anyway: record id by the record starts (usually the previous hit's record),
 // position, errors.
-void writeHits(const std::string& path, const std::vector<HitPart>& parts, bool emitErrors, unsigned nt) {
+void writeHits(const std::string& path, const std::vector<HitPart>& parts, bool emitErrors, unsigned nt,
+               uint32_t cigarLen = 0) {
     const int fd = ::open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
     if (fd < 0) throw CliError("can not open output file " + path);
     struct CloseFd {  // closed on every path out (formatting may throw, e.g. bad_alloc)
@@ -259,7 +262,7 @@ void writeHits(const std::string& path, const std::vector<HitPart>& parts, bool 
             };
             const Block& B = blocks[bi];
             try {
-                buf.resize((B.hi - B.lo) * 96);
+                buf.resize((B.hi - B.lo) * (cigarLen ? 256 : 96));
             } catch (...) {
                 failed.store(true);
                 publishEmpty();
@@ -267,7 +270,8 @@ void writeHits(const std::string& path, const std::vector<HitPart>& parts, bool 
             }
             char* o = buf.data();
             char* e = o + buf.size();
-            auto line = [&](uint64_t qid, uint64_t seq, uint64_t pos, uint32_t err) {
+            const HitPart& P = *B.part;
+            auto line = [&](uint64_t k, uint64_t qid, uint64_t seq, uint64_t pos, uint32_t err) {
                 o = std::to_chars(o, e, qid).ptr;
                 *o++ = ' ';
                 o = std::to_chars(o, e, seq).ptr;
@@ -277,13 +281,18 @@ void writeHits(const std::string& path, const std::vector<HitPart>& parts, bool 
                     *o++ = ' ';
                     o = std::to_chars(o, e, err).ptr;
                 }
+                if (cigarLen) {  // (at most 8 edits: < 150 characters)
+                    *o++ = ' ';
+                    const int n = sahara_cigar(&P.aln[k], cigarLen, o, (size_t)(e - o));
+                    if (n >= 0) o += n;
+                    else *o++ = '*';  // no alignment within the bound
+                }
                 *o++ = '\n';
             };
-            const HitPart& P = *B.part;
             if (!P.compact) {
                 for (uint64_t k = B.lo; k < B.hi; ++k) {
                     const sahara_hit& h = P.hits[k];
-                    line(h.qid + P.qidOffset, h.seq_id, h.pos, h.err);
+                    line(k, h.qid + P.qidOffset, h.seq_id, h.pos, h.err);
                 }
             } else {
                 const sahara_hit_blocks& H = P.blocks;
@@ -298,7 +307,7 @@ void writeHits(const std::string& path, const std::vector<HitPart>& parts, bool 
                         lo = S[seq];
                         hi = S[seq + 1];
                     }
-                    line(H.block_qid0[blk] + (v >> 36) + P.qidOffset, seq, g - lo, (uint32_t)(v & 15u));
+                    line(k, H.block_qid0[blk] + (v >> 36) + P.qidOffset, seq, g - lo, (uint32_t)(v & 15u));
                 }
             }
             const int64_t size = (int64_t)(o - buf.data());
@@ -385,6 +394,30 @@ std::string shortest(double v) {
     return std::string(b, r.ptr);
 }
 
+// The patterns of a shard as one rank per byte, the form sahara_gpu_align
+// takes: `rows` reads of len symbols from stream symbol sym0 of the 2-bit
+// codes (A C G T = 0 1 2 3, N positions listed), interleaved with their
+// reverse complements (rc) and cut to npat, as the search call forms them.
+std::vector<uint8_t> shardPatterns(const uint8_t* codes, uint64_t sym0, const uint64_t* npos, uint64_t ncount,
+                                   uint64_t rows, uint32_t len, bool rc, uint64_t npat, uint32_t sigma) {
+    const uint8_t rankOf[4] = {1, 2, 3, (uint8_t)(sigma == 6 ? 5 : 4)};
+    std::vector<uint8_t> reads(rows * len);
+    for (uint64_t i = 0; i < reads.size(); ++i) {
+        const uint64_t s = sym0 + i;
+        reads[i] = rankOf[(codes[s >> 2] >> (2 * (s & 3))) & 3];
+    }
+    const uint64_t* b = npos ? std::lower_bound(npos, npos + ncount, sym0) : nullptr;
+    for (; b && b < npos + ncount && *b < sym0 + reads.size(); ++b) reads[*b - sym0] = 4;
+    if (!rc) {
+        reads.resize(npat * len);
+        return reads;
+    }
+    std::vector<uint8_t> pats(2 * rows * len);
+    check(sahara_interleave_rc(reads.data(), rows, len, sigma, pats.data()), "interleaving reverse complements");
+    pats.resize(npat * len);
+    return pats;
+}
+
 struct Scheme {
     std::vector<uint32_t> pi, l, u;
     uint32_t n = 0;
@@ -410,9 +443,10 @@ int cmdSearch(int argc, char** argv) {
     Opt mode{{"-m", "--search_mode"}, false, "all"}, dist{{"-d", "--distance-metric"}, false, "lev"};
     Opt maxHits{{"--max_hits"}, false, "0"}, limit{{"--limit_queries"}};
     Opt gpus{{"--gpus"}, false, "1"}, emitErr{{"--emit-errors"}, true}, fmOnly{{"--fm-only"}, true};
+    Opt emitCigar{{"--emit-cigar"}, true};
     Parser p;
     for (Opt* o : {&query, &index, &output, &gen, &dyn, &errors, &noRev, &mode, &dist, &maxHits, &limit, &gpus,
-                   &emitErr, &fmOnly})
+                   &emitErr, &fmOnly, &emitCigar})
         p.add(*o);
     p.parse(argc, argv, 2);
     if (!p.positional.empty()) throw CliError("unexpected argument " + p.positional[0]);
@@ -425,6 +459,8 @@ int cmdSearch(int argc, char** argv) {
     const int k = (int)toU64(errors.value, "--errors");
     const long mh = std::strtol(maxHits.value.c_str(), nullptr, 10);
     const uint32_t ngpu = (uint32_t)std::max<uint64_t>(1, toU64(gpus.value, "--gpus"));
+    if (emitCigar.given && k > SAHARA_ALIGN_MAX_ERR)
+        throw CliError("--emit-cigar aligns at most " + std::to_string(SAHARA_ALIGN_MAX_ERR) + " errors (-e)");
 
     // sigma dispatch (search.cpp:276-291)
     const uint64_t sigma = readSigma(index.value);
@@ -621,7 +657,7 @@ int cmdSearch(int argc, char** argv) {
     // search + locate (search.cpp:218-250), reads sharded over the devices
     // (a read and its reverse complement stay together; qids stay global)
     std::vector<HitPart> parts(ngpu);
-    std::vector<double> devLocate(ngpu, 0.0), devSearch(ngpu, 0.0);
+    std::vector<double> devLocate(ngpu, 0.0), devSearch(ngpu, 0.0), devAlign(ngpu, 0.0);
     std::vector<std::string> errs(ngpu);
     {
         std::vector<std::thread> th;
@@ -675,7 +711,31 @@ int cmdSearch(int argc, char** argv) {
                 part.hits = hits;
                 part.n = nh;
                 part.qidOffset = q0;
-                parts[g] = part;  // released after writing
+                // --emit-cigar: the shard's hits aligned on its own device, before the merge. besthits
+                // searches with edit operations whatever -d says, so its hits align with them too
+                if (emitCigar.given && nh) {
+                    const auto tA = std::chrono::steady_clock::now();
+                    const int alignEdit = edit || besthits ? 1 : 0;
+                    try {
+                        part.aln.resize(nh);
+                        if (part.compact) {
+                            rc = sahara_gpu_align_packed_compact(ctx[g], reads, (uint64_t)r0 * len, npos, ncount,
+                                                                 r1 - r0, len, noRev.given ? 0 : 1, q1 - q0, alignEdit,
+                                                                 (uint32_t)k, &part.blocks, part.aln.data());
+                        } else {  // whole records (--max_hits, a multi-part index): the shard's patterns as ranks
+                            const std::vector<uint8_t> pats =
+                                shardPatterns(reads, (uint64_t)r0 * len, npos, ncount, r1 - r0, len, !noRev.given,
+                                              q1 - q0, (uint32_t)sigma);
+                            rc = sahara_gpu_align(ctx[g], pats.data(), q1 - q0, len, alignEdit, (uint32_t)k, hits, nh,
+                                                  part.aln.data());
+                        }
+                        if (rc != 0) errs[g] = sahara_gpu_last_error();
+                    } catch (const std::exception& ex) {
+                        errs[g] = ex.what();
+                    }
+                    devAlign[g] = std::chrono::duration<double>(std::chrono::steady_clock::now() - tA).count();
+                }
+                parts[g] = std::move(part);  // released after writing
             });
         }
         for (auto& t : th) t.join();
@@ -687,12 +747,14 @@ int cmdSearch(int argc, char** argv) {
         }
     double wall = sw.reset();
     const double loc = *std::max_element(devLocate.begin(), devLocate.end());
-    timing.emplace_back("search", std::max(0.0, wall - loc));
+    const double aln = *std::max_element(devAlign.begin(), devAlign.end());
+    timing.emplace_back("search", std::max(0.0, wall - loc - aln));
     timing.emplace_back("locate", loc);
+    if (emitCigar.given) timing.emplace_back("align", aln);
 
     uint64_t nhits = 0;
     for (auto& hp : parts) nhits += hp.n;
-    writeHits(output.value, parts, emitErr.given, nt);
+    writeHits(output.value, parts, emitErr.given, nt, emitCigar.given ? len : 0);
     for (auto& hp : parts) hp.release();
     timing.emplace_back("result", sw.reset());
     for (void*& c : ctx) {
@@ -752,7 +814,7 @@ void help() {
         "  sahara index <fasta> [--ignore_unknown] [--dna4] [--gpu N]\n"
         "  sahara search -q <fasta> -i <index> [-o <out>] [-g <generator>] [-e <k>] [--no-reverse]\n"
         "                [-m all|besthits] [-d ham|lev] [--max_hits <n>] [--limit_queries <n>]\n"
-        "                [--gpus <N>] [--emit-errors] [--fm-only]\n"
+        "                [--gpus <N>] [--emit-errors] [--emit-cigar] [--fm-only]\n"
         "  sahara read_simulator -o <fasta> [-i <reference>] [-l <len>] [-n <reads>] [-e <errors>]\n"
         "                [--substitution_errors n] [--insertion_errors n] [--deletion_errors n]\n"
         "                [--fasta_line_length n] [--seed s]\n"

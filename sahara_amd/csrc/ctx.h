@@ -366,6 +366,22 @@ struct Ctx {
         std::vector<RoundEvents> earlier;
     } slot[kSlots];
 
+    // sahara_gpu_align[_packed_compact]: the call's patterns, whole, as
+    // 3-bit-plane blocks (one spare block after the last: align.h), with the
+    // staging they are packed from (rank bytes; 2-bit codes, their N list and
+    // the 4-bit twin kPackFrom2 writes beside the blocks); one chunk of hit
+    // records going up and of alignment records coming down; a compact call's
+    // blocks (block_end, then block_qid0)
+    struct Align {
+        DevBuf<uint4> pats3;
+        DevBuf<uint8_t> raw;
+        DevBuf<uint32_t> nList, pats4;
+        DevBuf<char> in;
+        DevBuf<sahara_alignment> out;
+        DevBuf<uint64_t> blocks;
+        sahara_align_stats stats{};
+    } align;
+
     // Streams, events and page-locked memory: declared last, released first
     // (the rule at the top of Ctx).
     Stream st, stB, stC, stD;  // FM phase and single-stream work; text, locate / sort, seeds
