@@ -17,8 +17,9 @@ BUILD_ID := $(shell python3 tools/build_id.py)
 $(shell mkdir -p $(OBJDIR) && echo '#define SAHARA_BUILD_ID "$(BUILD_ID)"' > $(OBJDIR)/build_id.h.new && \
         (cmp -s $(OBJDIR)/build_id.h.new $(OBJDIR)/build_id.h || mv $(OBJDIR)/build_id.h.new $(OBJDIR)/build_id.h))
 
-OBJS := $(OBJDIR)/index_build.o $(OBJDIR)/search.o $(OBJDIR)/align.o $(OBJDIR)/capi.o $(OBJDIR)/staging.o $(OBJDIR)/pass.o \
-        $(OBJDIR)/host_util.o $(OBJDIR)/scheme.o
+# the library's translation units (csrc/NAME.hip or .cpp), listed once for the plain and the sanitizer build
+UNITS := index_build search align capi capi_ctx capi_align capi_synth staging pass host_util scheme
+OBJS  := $(UNITS:%=$(OBJDIR)/%.o)
 
 all: $(LIB) oracle $(if $(wildcard sahara_amd/cli/*.cpp),$(CLI),) tools/gather_bench
 
@@ -30,8 +31,9 @@ $(OBJDIR)/%.o: $(CSRC)/%.cpp $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(OBJDIR)/capi.o: $(OBJDIR)/build_id.h
-$(OBJDIR)/capi.o: HIPFLAGS += -include $(OBJDIR)/build_id.h
+# (sahara_build_id lives in capi_ctx.cpp)
+$(OBJDIR)/capi_ctx.o: $(OBJDIR)/build_id.h
+$(OBJDIR)/capi_ctx.o: HIPFLAGS += -include $(OBJDIR)/build_id.h
 
 $(LIB): $(OBJS)
 	@mkdir -p $(LIBDIR)
@@ -53,8 +55,7 @@ oracle:
 # test suite against them.
 ASAN_HOST := -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined -Xarch_host -fno-omit-frame-pointer
 ASANDIR   := build/asan
-ASAN_OBJS := $(ASANDIR)/index_build.o $(ASANDIR)/search.o $(ASANDIR)/align.o $(ASANDIR)/capi.o $(ASANDIR)/staging.o $(ASANDIR)/pass.o \
-             $(ASANDIR)/host_util.o $(ASANDIR)/scheme.o
+ASAN_OBJS := $(UNITS:%=$(ASANDIR)/%.o)
 
 $(ASANDIR)/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(ASANDIR)
@@ -64,8 +65,8 @@ $(ASANDIR)/%.o: $(CSRC)/%.cpp $(HDRS)
 	@mkdir -p $(ASANDIR)
 	$(HIPCC) $(HIPFLAGS) -O1 $(ASAN_HOST) -c $< -o $@
 
-$(ASANDIR)/capi.o: $(OBJDIR)/build_id.h
-$(ASANDIR)/capi.o: HIPFLAGS += -include $(OBJDIR)/build_id.h
+$(ASANDIR)/capi_ctx.o: $(OBJDIR)/build_id.h
+$(ASANDIR)/capi_ctx.o: HIPFLAGS += -include $(OBJDIR)/build_id.h
 
 $(ASANDIR)/libsahara_hip.so: $(ASAN_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(ASAN_OBJS) -o $@ -lpthread

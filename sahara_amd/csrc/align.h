@@ -9,7 +9,7 @@
 namespace sahara {
 
 // One launch of kAlignHits over a chunk of hit records of one index part.
-// The records were checked before (capi.cpp): every qid names a pattern,
+// The records were checked before (capi_align.cpp): every qid names a pattern,
 // every position lies in the text.
 struct AlignArgs {
     const uint4* text3;        // the part's text as 3-bit-plane blocks (device_index.h)

@@ -1,46 +1,33 @@
-// capi.cpp — the C ABI of libsahara_hip.so (include/sahara_hip.h).
+// capi.cpp — the search calls of libsahara_hip.so's C ABI (include/sahara_hip.h)
+// and the host buffers their hits leave in. The context and index calls are
+// in capi_ctx.cpp, alignment in capi_align.cpp, the synthetic-data and
+// host-only helpers in capi_synth.cpp.
 //
 // The drop-in boundary for sahara's hot path: index residency
 // (search.cpp:162-169), GPU index construction (index.cpp:87-100), and
 // search + locate (search.cpp:218-250). No C++ types or exceptions cross it.
 
 #include <hip/hip_runtime.h>
-#include <immintrin.h>
 #include <sys/mman.h>
 
 #include <algorithm>
 #include <chrono>
-#include <cctype>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <fstream>
 #include <memory>
-#include <condition_variable>
-#include <functional>
 #include <mutex>
-#include <random>
-#include <unordered_map>
+#include <optional>
 #include <string>
-#include <atomic>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
-#include "../../include/sahara_hip.h"
-#include "device_index.h"
-#include "idx_format.h"
-#include <sys/syscall.h>
-#include <unistd.h>
-
-#include "align.h"
 #include "ctx.h"
-#include "search.h"
 
 using namespace sahara;
 
 namespace sahara {
-
-thread_local std::string g_err;
 
 bool hitLess(const sahara_hit& a, const sahara_hit& b) {
     if (a.qid != b.qid) return a.qid < b.qid;
@@ -81,419 +68,12 @@ void handOver(const std::vector<sahara_hit>& v, sahara_hit** hits, uint64_t* n_h
     *n_hits = v.size();
 }
 
-// SAHARA_DEVICE_MAP=a,b,c (test hook): context device d opens HIP device
-// list[d], so that `sahara search --gpus N` and concurrent contexts run their
-// multi-device code path on one GPU (tests/test_multi_device.py)
-static int mapDevice(int device) {
-    const char* e = std::getenv("SAHARA_DEVICE_MAP");
-    if (!e || !*e) return device;
-    std::vector<int> map;
-    for (const char* p = e; *p;) {
-        char* end = nullptr;
-        const long v = std::strtol(p, &end, 10);
-        if (end == p) throw Error(std::string("SAHARA_DEVICE_MAP: not a list of device numbers: ") + e);
-        map.push_back((int)v);
-        p = *end == ',' ? end + 1 : end;
-        if (*end && *end != ',') throw Error(std::string("SAHARA_DEVICE_MAP: not a list of device numbers: ") + e);
-    }
-    if (device < 0 || (size_t)device >= map.size())
-        throw Error("SAHARA_DEVICE_MAP has no entry for device " + std::to_string(device));
-    return map[(size_t)device];
-}
-
-// The CPUs of NUMA node `node` that this process may run on.
-Placement placementOfNode(int node) {
-    Placement pl;
-    pl.node = node;
-    if (node < 0) return pl;
-    std::FILE* f = std::fopen(("/sys/devices/system/node/node" + std::to_string(node) + "/cpulist").c_str(), "r");
-    if (!f) return pl;
-    char buf[8192] = {0};
-    const size_t got = std::fread(buf, 1, sizeof(buf) - 1, f);
-    std::fclose(f);
-    buf[got] = 0;
-    cpu_set_t allowed;
-    CPU_ZERO(&allowed);
-    if (sched_getaffinity(0, sizeof(allowed), &allowed) != 0) return pl;
-    cpu_set_t set;
-    CPU_ZERO(&set);
-    for (const char* p = buf; *p && *p != '\n';) {  // "0-15,64-79"
-        char* end = nullptr;
-        const long a = std::strtol(p, &end, 10);
-        if (end == p) break;
-        long b = a;
-        if (*end == '-') b = std::strtol(end + 1, &end, 10);
-        for (long i = a; i <= b && i < CPU_SETSIZE; ++i)
-            if (CPU_ISSET(i, &allowed)) CPU_SET(i, &set);
-        p = *end == ',' ? end + 1 : end;
-    }
-    pl.cpus = set;
-    pl.ncpus = CPU_COUNT(&set);
-    return pl;
-}
-
-// The CPUs of the device's NUMA node that this process may run on (Placement).
-static void placeNear(Ctx* c) {
-    const char* e = std::getenv("SAHARA_NUMA");
-    if (e && std::atoi(e) == 0) return;
-    char bdf[64] = {0};
-    if (hipDeviceGetPCIBusId(bdf, sizeof(bdf), c->device) != hipSuccess) {
-        (void)hipGetLastError();
-        return;
-    }
-    std::string id(bdf);
-    for (char& ch : id) ch = (char)std::tolower((unsigned char)ch);
-    int node = -1;
-    if (std::FILE* f = std::fopen(("/sys/bus/pci/devices/" + id + "/numa_node").c_str(), "r")) {
-        if (std::fscanf(f, "%d", &node) != 1) node = -1;
-        std::fclose(f);
-    }
-    c->place = placementOfNode(node);
-}
-
-// host threads a context uses for one job: its node's allowed CPUs (or the
-// process's), at most cap
-unsigned hostThreads(const Ctx* c, unsigned cap) {
-    unsigned n = (unsigned)c->place.ncpus;
-    if (n == 0) {
-        cpu_set_t s;
-        CPU_ZERO(&s);
-        n = sched_getaffinity(0, sizeof(s), &s) == 0 ? (unsigned)CPU_COUNT(&s) : std::thread::hardware_concurrency();
-    }
-    return std::max(1u, std::min(cap, n));
-}
-
-Ctx* newCtx(int device) {
-    int n = 0;
-    SH_HIP(hipGetDeviceCount(&n));
-    const int hipDev = mapDevice(device);
-    if (hipDev < 0 || hipDev >= n)
-        throw Error("no HIP device " + std::to_string(hipDev) + " (found " + std::to_string(n) + ")");
-    SH_HIP(hipSetDevice(hipDev));
-    auto c = std::make_unique<Ctx>();
-    c->device = hipDev;
-    placeNear(c.get());
-    hipDeviceProp_t prop;
-    SH_HIP(hipGetDeviceProperties(&prop, hipDev));
-    if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos)
-        throw Error(std::string("libsahara_hip is built for gfx950 (MI355X); device is ") + prop.gcnArchName);
-    c->numCU = prop.multiProcessorCount;
-    // (No stream gets a CU mask: with a CU-masked stream in the process the
-    // memory-bound kernels on the other streams ran 1.4-1.8x longer, r5.)
-    for (Stream* s : {&c->st, &c->stB, &c->stC, &c->stD, &c->stE, &c->stF}) *s = Stream(hipStreamNonBlocking);
-    for (Event* e : {&c->outCopied[0], &c->outCopied[1], &c->locStart, &c->locDone, &c->sortDone, &c->totalsDown,
-                     &c->flagsDown, &c->recsMade})
-        *e = Event(hipEventDefault);
-    for (Event* e : {&c->totalsDownSleep, &c->flagsDownSleep}) *e = Event(hipEventDisableTiming | hipEventBlockingSync);
-    for (auto& e : c->ringEv) e = Event(hipEventDisableTiming);
-    // the streamed upload's pinned ring, pinned while the caller builds or
-    // loads the index (pinning 256 MB takes ~50 ms)
-    Ctx* raw = c.get();
-    raw->ringInit = std::thread([raw] {
-        raw->place.bind();  // pinned pages first touched on the device's node
-        (void)hipSetDevice(raw->device);
-        try {
-            raw->ring.reserve(Ctx::kRingSlots * Ctx::kRingSlot, hipHostMallocPortable);
-        } catch (const Error&) {
-            raw->ringFailed = true;
-        }
-        try {
-            raw->downRing.reserve(Ctx::kDownSlots * Ctx::kDownSlot / sizeof(uint64_t), hipHostMallocPortable);
-        } catch (const Error&) {  // no compact download: hits go to a pinned sink whole
-        }
-    });
-    for (auto& sl : c->slot) {
-        for (Event* e : {&sl.fmStart, &sl.seedDone, &sl.seedDone0, &sl.seedMid, &sl.fmBegin, &sl.fmDone, &sl.textStart,
-                         &sl.textDone, &sl.free, &sl.textMid0, &sl.textMid1})
-            *e = Event(hipEventDefault);
-        sl.small.reserve(kSlotWords);
-        sl.queues.reserve(kQueuesWords);
-    }
-    for (auto& p : c->outStage) p.reserve(Ctx::kOutChunk);
-    c->small.reserve(8);
-    c->counters.reserve(kCounters);
-    SH_HIP(hipMemset(c->counters.ptr, 0, kCounters * sizeof(unsigned long long)));
-    return c.release();
-}
-
-Ctx* ctxOf(void* p) {
-    if (!p) throw Error("null context");
-    Ctx* c = static_cast<Ctx*>(p);
-    SH_HIP(hipSetDevice(c->device));
-    return c;
-}
-
-// an .idx image (one part or several) -> a context holding every part
-Ctx* openImage(int device, const uint8_t* buf, size_t bytes) {
-    const auto t0 = std::chrono::steady_clock::now();
-    auto since = [&t0] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
-    const std::vector<IdxParts> parts = parseIdxAll(buf, bytes);
-    const double tParse = since();
-    std::unique_ptr<Ctx> c(newCtx(device));
-    const double tCtx = since();
-    if (std::getenv("SAHARA_TIMING"))  // (the parts' own steps follow from buildFromParts)
-        std::fprintf(stderr, "[sahara] open: parse %.1f ms, context %.1f ms\n", tParse, tCtx - tParse);
-    uint64_t rec0 = 0, nmax = 0;
-    c->partRec0.clear();
-    // the image's arrays through the pinned ring (SAHARA_LOAD_RING=0: pageable copies)
-    Ctx* raw = c.get();
-    const HostUpload viaRing = [raw](void* dst, const void* src, size_t n, hipStream_t s) {
-        uploadViaRing(raw, dst, src, n, s);
-    };
-    const char* lr = std::getenv("SAHARA_LOAD_RING");
-    const HostUpload* up = lr && std::atoi(lr) == 0 ? nullptr : &viaRing;
-    for (size_t p = 0; p < parts.size(); ++p) {
-        const IdxParts& P = parts[p];
-        if (p) c->more.emplace_back();
-        buildFromParts(partOf(c.get(), (uint32_t)p), P.sigma, P.n, P.recLens.data(), P.recLens.size(), P.rate, P.bwtF,
-                       P.bwtR, P.sampled, P.samples, P.nsamples, c->st, parts.size() == 1, up);
-        c->partRec0.push_back(rec0);
-        rec0 += P.recLens.size();
-        nmax = std::max(nmax, P.n);
-    }
-    if (parts.size() > 1) {
-        const uint32_t K = kmerDepth(nmax, (uint32_t)parts.size());
-        for (uint32_t p = 0; p < parts.size(); ++p) buildKmerTable(partOf(c.get(), p), K, c->st);
-    }
-    return c.release();
-}
-
 // SAHARA_TIMING=2: a call's host-side marks (Ctx::mark), from t0 on, printed (stderr) at its end
 static void traceBegin(Ctx* c, std::chrono::steady_clock::time_point t0) {
     const char* te = std::getenv("SAHARA_TIMING");
     c->traceOn = te && std::atoi(te) >= 2;
     c->traceT0 = t0;
     c->trace.clear();
-}
-
-}  // namespace sahara
-
-extern "C" {
-
-const char* sahara_gpu_last_error(void) { return g_err.c_str(); }
-
-const char* sahara_build_id(void) { return SAHARA_BUILD_ID; }
-
-int sahara_gpu_device_count(void) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
-}
-
-int sahara_gpu_build(int device, const uint8_t* ranks, const uint64_t* rec_lens, uint64_t n_records, uint32_t sigma,
-                     uint32_t sampling_rate, void** ctx) {
-    return guarded([&] {
-        std::unique_ptr<Ctx> c(newCtx(device));
-        const std::vector<uint64_t> first = splitRecords(rec_lens, n_records);
-        if (first.size() == 2) {
-            buildFromText(c->I, ranks, rec_lens, n_records, sigma, sampling_rate, c->st);
-        } else {  // parts at record boundaries, then their k-mer tables at one common depth
-            uint64_t off = 0, nmax = 0;
-            for (size_t p = 0; p + 1 < first.size(); ++p) {
-                uint64_t syms = 0, n = 0;
-                for (uint64_t r = first[p]; r < first[p + 1]; ++r) syms += rec_lens[r];
-                n = syms + (first[p + 1] - first[p]);
-                nmax = std::max(nmax, n);
-                if (p) c->more.emplace_back();
-                buildFromText(partOf(c.get(), (uint32_t)p), ranks + off, rec_lens + first[p], first[p + 1] - first[p],
-                              sigma, sampling_rate, c->st, false);
-                off += syms;
-            }
-            c->partRec0.assign(first.begin(), first.end() - 1);
-            const uint32_t K = kmerDepth(nmax, (uint32_t)first.size() - 1);
-            for (uint32_t p = 0; p + 1 < first.size(); ++p) buildKmerTable(partOf(c.get(), p), K, c->st);
-        }
-        *ctx = c.release();
-    });
-}
-
-int sahara_gpu_open(int device, const void* idx_image, size_t idx_bytes, void** ctx) {
-    return guarded([&] { *ctx = openImage(device, static_cast<const uint8_t*>(idx_image), idx_bytes); });
-}
-
-int sahara_gpu_open_file(int device, const char* path, void** ctx) {
-    return guarded([&] {
-        const std::vector<uint8_t> buf = readFile(path);
-        *ctx = openImage(device, buf.data(), buf.size());
-    });
-}
-
-int sahara_gpu_index_info(void* ctx, sahara_index_info* info) {
-    return guarded([&] {
-        Ctx* c = ctxOf(ctx);
-        info->sigma = c->I.sigma;
-        info->sampling_rate = c->I.rate;
-        info->n = info->n_records = info->n_samples = info->device_bytes = 0;
-        for (uint32_t p = 0; p <= c->more.size(); ++p) {  // totals over the parts
-            const DeviceIndex& D = partOf(c, p);
-            info->n += D.n;
-            info->n_records += D.recLens.size();
-            info->n_samples += D.nsamples;
-            info->device_bytes += D.deviceBytes();
-        }
-        info->n_parts = (uint32_t)c->more.size() + 1;
-        info->kmer_depth = c->I.kmerK;
-    });
-}
-
-int sahara_gpu_export(void* ctx, uint8_t* bwt_f, uint8_t* bwt_r, uint64_t* sampled_bits, uint32_t* samples,
-                      uint64_t* C, uint64_t* rec_lens) {
-    return guarded([&] {
-        Ctx* c = ctxOf(ctx);
-        DeviceIndex& D = partOf(c, c->exportPart);
-        exportParts(D, bwt_f, bwt_r, sampled_bits, samples, c->st);
-        if (C) std::memcpy(C, D.C, (D.sigma + 1) * 8);
-        if (rec_lens) std::memcpy(rec_lens, D.recLens.data(), D.recLens.size() * 8);
-    });
-}
-
-int sahara_gpu_export_sa(void* ctx, uint32_t* sa) {
-    return guarded([&] {
-        const DeviceIndex& D = partOf(ctxOf(ctx), ctxOf(ctx)->exportPart);
-        SH_HIP(hipMemcpy(sa, D.saFull.ptr, D.n * 4, hipMemcpyDeviceToHost));
-    });
-}
-
-int sahara_gpu_export_text(void* ctx, uint8_t* text) {
-    return guarded([&] {
-        const DeviceIndex& D = partOf(ctxOf(ctx), ctxOf(ctx)->exportPart);
-        std::vector<uint32_t> t3(((D.n + 31) / 32) * 4);
-        SH_HIP(hipMemcpy(t3.data(), D.text3.ptr, t3.size() * 4, hipMemcpyDeviceToHost));
-        for (uint64_t i = 0; i < D.n; ++i) {
-            const uint32_t* b = &t3[(i / 32) * 4];
-            const uint32_t j = (uint32_t)(i & 31);
-            text[i] = (uint8_t)(((b[0] >> j) & 1u) | (((b[1] >> j) & 1u) << 1) | (((b[2] >> j) & 1u) << 2));
-        }
-    });
-}
-
-int sahara_gpu_part_info(void* ctx, uint32_t part, sahara_index_info* info) {
-    return guarded([&] {
-        Ctx* c = ctxOf(ctx);
-        if (part > c->more.size()) throw Error("no index part " + std::to_string(part));
-        const DeviceIndex& D = partOf(c, part);
-        info->sigma = D.sigma;
-        info->sampling_rate = D.rate;
-        info->n = D.n;
-        info->n_records = D.recLens.size();
-        info->n_samples = D.nsamples;
-        info->device_bytes = D.deviceBytes();
-        info->n_parts = (uint32_t)c->more.size() + 1;
-        info->kmer_depth = D.kmerK;
-    });
-}
-
-int sahara_gpu_select_part(void* ctx, uint32_t part) {
-    return guarded([&] {
-        Ctx* c = ctxOf(ctx);
-        if (part > c->more.size()) throw Error("no index part " + std::to_string(part));
-        c->exportPart = part;
-    });
-}
-
-int sahara_gpu_set_mode(void* ctx, int verify, int locate_sa) {
-    return guarded([&] {
-        Ctx* c = ctxOf(ctx);
-        c->verify = verify != 0;
-        c->locateSA = locate_sa != 0;
-    });
-}
-
-int sahara_gpu_save(void* ctx, const char* path) {
-    return guarded([&] {
-        Ctx* c = ctxOf(ctx);
-        const size_t np = c->more.size() + 1;
-        std::vector<std::vector<uint8_t>> bf(np), br(np);
-        std::vector<std::vector<uint64_t>> sb(np);
-        std::vector<std::vector<uint32_t>> smp(np);
-        std::vector<IdxParts> parts(np);
-        for (uint32_t p = 0; p < np; ++p) {
-            const DeviceIndex& D = partOf(c, p);
-            const uint64_t n = D.n;
-            bf[p].resize(n);
-            br[p].resize(n);
-            sb[p].resize(n / 64 + 1);
-            smp[p].resize(D.nsamples);
-            exportParts(D, bf[p].data(), br[p].data(), sb[p].data(), smp[p].data(), c->st);
-            IdxParts& P = parts[p];
-            P.sigma = D.sigma;
-            P.n = n;
-            P.rate = D.rate;
-            std::copy(D.C, D.C + 8, P.C);
-            P.recLens = D.recLens;
-            P.bwtF = bf[p].data();
-            P.bwtR = br[p].data();
-            P.sampled = sb[p].data();
-            P.samples = smp[p].data();
-            P.nsamples = smp[p].size();
-        }
-        writeIdxAll(path, parts);
-    });
-}
-
-int sahara_gpu_stage(void* ctx, const uint8_t* ranks, uint64_t n_patterns, uint32_t len, const uint32_t* pi,
-                     const uint32_t* l, const uint32_t* u, uint32_t n_searches, int edit) {
-    return guarded([&] { stage(ctxOf(ctx), ranks, n_patterns, len, pi, l, u, &n_searches, 1, edit); });
-}
-
-int sahara_gpu_run(void* ctx, int count, uint64_t* n_hits) {
-    return guarded([&] {
-        Ctx* c = ctxOf(ctx);
-        traceBegin(c, std::chrono::steady_clock::now());
-        run(c, count != 0);
-        if (n_hits) *n_hits = c->nout;
-        if (c->traceOn) {
-            c->mark("run returns", 0);
-            std::sort(c->trace.begin(), c->trace.end());
-            for (auto& m : c->trace) std::fprintf(stderr, "[sahara]   %8.3f %s\n", m.first, m.second.c_str());
-            c->traceOn = false;
-        }
-    });
-}
-
-int sahara_gpu_fetch(void* ctx, sahara_hit* out, uint64_t capacity, uint64_t* n_hits) {
-    return guarded([&] {
-        Ctx* c = ctxOf(ctx);
-        if (n_hits) *n_hits = c->nout;
-        if (capacity < c->nout) throw Error("sahara_gpu_fetch: capacity too small");
-        if (c->nout) SH_HIP(hipMemcpy(out, c->wholeHits(), c->nout * sizeof(sahara_hit), hipMemcpyDeviceToHost));
-    });
-}
-
-int sahara_gpu_copy_hits(void* ctx, void* dst_device, uint64_t capacity, uint64_t qid_offset, uint64_t* n_hits) {
-    return guarded([&] {
-        Ctx* c = ctxOf(ctx);
-        if (n_hits) *n_hits = c->nout;
-        if (capacity < c->nout) throw Error("sahara_gpu_copy_hits: capacity too small");
-        if (c->nout && !dst_device) throw Error("sahara_gpu_copy_hits: null destination");
-        launchCopyHits(c->wholeHits(), c->nout, qid_offset, static_cast<sahara_hit*>(dst_device), c->st);
-        SH_HIP(hipStreamSynchronize(c->st));
-    });
-}
-
-int sahara_gpu_digest(void* ctx, uint64_t* digest) {
-    return guarded([&] {
-        Ctx* c = ctxOf(ctx);
-        SH_HIP(hipMemsetAsync(c->counters.ptr + 4, 0, 8, c->st));
-        launchDigest(c->wholeHits(), c->nout, c->counters.ptr + 4, c->st);
-        unsigned long long d = 0;
-        SH_HIP(hipMemcpyAsync(&d, c->counters.ptr + 4, 8, hipMemcpyDeviceToHost, c->st));
-        SH_HIP(hipStreamSynchronize(c->st));
-        *digest = d;
-    });
-}
-
-int sahara_gpu_placement(void* ctx, int* device, int* numa_node, int* n_cpus) {
-    return guarded([&] {
-        Ctx* c = ctxOf(ctx);
-        if (device) *device = c->device;
-        if (numa_node) *numa_node = c->place.node;
-        if (n_cpus) *n_cpus = c->place.ncpus;
-    });
-}
-
-int sahara_gpu_stats(void* ctx, sahara_stats* stats) {
-    return guarded([&] { *stats = ctxOf(ctx)->stats; });
 }
 
 // Hit buffers handed to the caller. Buffers of >= 64 MB are page-locked
@@ -507,15 +87,23 @@ struct HitPool {
     std::unordered_map<void*, size_t> live;       // pinned buffers the callers hold
     std::vector<std::pair<void*, size_t>> idle;   // pinned buffers ready for reuse
     static constexpr size_t kKeep = 2;
+    // the size of an idle buffer that holds `bytes` (the last such), 0: none does
+    size_t idleHolding(size_t bytes) {
+        std::lock_guard<std::mutex> g(mu);
+        size_t found = 0;
+        for (auto& e : idle)
+            if (e.second >= bytes) found = e.second;
+        return found;
+    }
 };
 static HitPool& hitPool() {
     static HitPool* p = new HitPool;  // never destroyed: callers may free after static destructors ran
     return *p;
 }
 
-// Host buffer of `bytes` (released with sahara_gpu_free); *pinned tells
-// whether the device can copy (or write) into it directly; *capBytes its size.
-static void* allocPinned(size_t bytes, bool* pinned, size_t* capBytes, bool mayPin, bool always = false);
+// allocPinned (ctx.h): host buffer of `bytes` (released with sahara_gpu_free);
+// *pinned tells whether the device can copy (or write) into it directly;
+// *capBytes its size.
 
 // Host buffer for n hits (released with sahara_gpu_free).
 static void* allocHits(uint64_t n, bool* pinned, uint64_t* capHits = nullptr, bool mayPin = true) {
@@ -526,7 +114,7 @@ static void* allocHits(uint64_t n, bool* pinned, uint64_t* capHits = nullptr, bo
 }
 
 // always: pinned whatever the size (a sink the device writes into)
-static void* allocPinned(size_t bytes, bool* pinned, size_t* capBytes, bool mayPin, bool always) {
+void* allocPinned(size_t bytes, bool* pinned, size_t* capBytes, bool mayPin, bool always) {
     bytes = std::max<size_t>(bytes, 1);
     *pinned = false;
     *capBytes = bytes;
@@ -571,7 +159,7 @@ static void* allocPinned(size_t bytes, bool* pinned, size_t* capBytes, bool mayP
     return p;
 }
 
-static void freeHits(void* p) {
+void freeHits(void* p) {
     if (!p) return;
     HitPool& P = hitPool();
     void* drop = nullptr;
@@ -612,7 +200,7 @@ static void parallelCopy(void* dst, const void* src, size_t bytes) {
 // Device hits -> pageable host memory through two pinned chunks: chunk k's
 // DMA runs while the host copies chunk k-1 out (a direct copy to pageable
 // memory runs at ~10 GB/s).
-static void copyOut(Ctx* c, void* dst, const void* src, size_t bytes) {
+void copyOut(Ctx* c, void* dst, const void* src, size_t bytes) {
     if (bytes < (8u << 20)) {
         SH_HIP(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
         return;
@@ -660,13 +248,7 @@ static void traceEnd(Ctx* c) {
     c->traceOn = false;
 }
 
-// The query list of a reads call: n_reads reads, interleaved with their
-// reverse complements (reverse) and cut to `limit` patterns (--limit_queries
-// cuts the interleaved list, search.cpp:125-127); rows: the reads it takes.
-struct ReadRows {
-    uint64_t npat, rows;
-};
-static ReadRows readRows(int reverse, uint64_t n_reads, uint64_t limit) {
+ReadRows readRows(int reverse, uint64_t n_reads, uint64_t limit) {
     uint64_t npat = reverse ? 2 * n_reads : n_reads;
     if (limit && limit < npat) npat = limit;
     if (npat == 0) throw Error("no patterns");
@@ -679,18 +261,15 @@ static uint64_t sinkEstimate(const Ctx* c, uint64_t npat) {
     return c && c->lastHits ? c->lastHits + c->lastHits / 8 + 1024 : 2 * npat + 1024;
 }
 
-// a host buffer on its way to the caller, freed by freeHits (allocHits, allocPinned) or std::free
-using HostBuf = std::unique_ptr<void, void (*)(void*)>;
-
-// A streamed call fails after staging (the guard of searchStreamed and
-// searchReadsCompact): when this returns nothing of the call runs, reads the
-// caller's queries or writes into its sink, which the caller's owner frees
-// next (it is declared before the guard), and nothing stays staged.
+// A streamed call fails after staging (the guard of streamedCall): when this
+// returns nothing of the call runs, reads the caller's queries or writes into
+// its sink, which the caller's owner frees next (it is declared before the
+// guard), and nothing stays staged.
 // packingOnly: no pass was started, only chunks may be packing ahead.
 static void abandonCall(Ctx* c, bool packingOnly) {
     if (packingOnly) drainPacking(c);
     else drainAll(c);
-    if (c->sk.compact) {
+    if (c->sk.route == HitRoute::Expander) {
         try {
             c->expander->drain();
         } catch (...) {
@@ -699,9 +278,6 @@ static void abandonCall(Ctx* c, bool packingOnly) {
     c->sk = {};
 }
 
-// sahara_gpu_search / sahara_gpu_search_reads: streamed upload, the pipelined
-// pass, the hits streamed into a pinned host sink batch by batch, then handed
-// to the caller (search.cpp:218-250 from host queries to host hits).
 // The scheme(s) of a call: one, or the exact-j schemes of a besthits call back
 // to back, which the pass runs as rounds within each batch (pass.cpp).
 struct Schemes {
@@ -716,74 +292,82 @@ struct Schemes {
     }
 };
 
-static void searchStreamed(Ctx* c, const uint8_t* src, uint64_t rows, bool rc, uint64_t npat, uint32_t len,
-                           const Schemes& sc, uint32_t max_hits, sahara_hit** hits, uint64_t* n_hits,
-                           const PackedReads* packed = nullptr) {
-    using clk = std::chrono::steady_clock;
-    const auto tA = clk::now();
-    traceBegin(c, tA);
-    HostBuf sink(nullptr, freeHits);
-    stageStreamed(c, src, rows, rc, npat, len, sc.pi, sc.l, sc.u, sc.ns, sc.n, sc.edit, packed);
-    ScopeExit failed([c] { abandonCall(c, false); });
-    const auto tB = clk::now();
-    // --max_hits: per batch on the device (limitBatch), so the limited hits
-    // stream to the host like any others; a multi-part index limits after
-    // its parts merge, on the host (limitHits)
-    const bool hostLimit = max_hits && !c->more.empty();
-    c->sk.limitN = hostLimit ? 0u : max_hits;
-    if (!hostLimit) {
+// The queries of a streamed call: `rows` source rows of `len` symbols (ranks,
+// or 2-bit codes with `packed`), which make npat patterns (rc: each row and
+// its reverse complement).
+struct Queries {
+    const uint8_t* src;
+    uint64_t rows;
+    bool rc;
+    uint64_t npat;
+    uint32_t len;
+    const PackedReads* packed;
+};
+
+using clk = std::chrono::steady_clock;
+static double msBetween(clk::time_point a, clk::time_point b) {
+    return std::chrono::duration<double, std::milli>(b - a).count();
+}
+struct CallTimes {
+    clk::time_point start, staged, sinkOpen, passDone;
+};
+
+// The two shapes in which a streamed call's hits leave (streamedCall below).
+// Each opens its sink before the pass: the host buffer, c->sk.host / cap and
+// the route; and collects after it: whatever the sink did not take during
+// the pass, then the hand-over to the caller. The buffer belongs to the shape,
+// which the caller declares before the driver's guard: it is freed after
+// everything that could write into it has stopped.
+
+// Whole hits, returned as sahara_hit** (sahara_gpu_search and its kin): each
+// batch's hits into a pooled host buffer during the pass (hit_route.h
+// callRoute), the rest after it.
+struct WholeHits {
+    uint32_t maxHits;
+    sahara_hit** hits;
+    uint64_t* nHits;
+    HostBuf sink{nullptr, freeHits};
+    bool pinned = false;     // the device copies into `sink` directly
+    bool hostLimit = false;  // --max_hits on the merged hits of a multi-part index (limitHits)
+
+    void openSink(Ctx* c, uint64_t npat) {
+        // --max_hits: per batch on the device (limitBatch), so the limited hits
+        // stream to the host like any others; a multi-part index limits after
+        // its parts merge, on the host (limitHits)
+        hostLimit = maxHits && !c->more.empty();
+        c->sk.limitN = hostLimit ? 0u : maxHits;
+        if (hostLimit) return;
         // a first call takes a pooled buffer if there is one, but pins none:
         // pinning ~1 GB costs ~200 ms, ten times the pageable copy-out
-        bool pinned = false;
-        HostBuf p(allocHits(sinkEstimate(c, npat), &pinned, &c->sk.cap, c->lastHits != 0), freeHits);
-        // hits go whole into a pinned sink (DMA; no host CPU or memory traffic
-        // beyond the write), or, into pageable memory, as 8-B records that
-        // host threads expand (Expander): a third of the PCIe bytes, but the
-        // expansion reads and writes host memory the packing also needs
-        // (at C3 it took ~4 ms per batch beside the packing, 300M against
-        // 330M reads/s). SAHARA_COMPACT_DOWNLOAD=1 / SAHARA_FULL_DOWNLOAD=1 force one.
+        uint64_t cap = 0;
+        HostBuf p(allocHits(sinkEstimate(c, npat), &pinned, &cap, c->lastHits != 0), freeHits);
         const bool compactOk = c->downRing.ptr && c->maxErr < 16 && c->I.n < (1ull << 32);
         const char* fe = std::getenv("SAHARA_FULL_DOWNLOAD");
         const char* ce = std::getenv("SAHARA_COMPACT_DOWNLOAD");
-        const bool compact = compactOk && !(fe && std::atoi(fe)) && (!pinned || (ce && std::atoi(ce)));
-        if (p && (pinned || compact)) {
-            sink = std::move(p);
-            c->sk.sink = static_cast<sahara_hit*>(sink.get());
-            c->sk.pinned = pinned;
-            c->sk.compact = compact;
-        } else {
-            c->sk.cap = 0;
-        }
-        if (c->sk.compact) {
+        const CallRoute r = callRoute(pinned, compactOk, fe && std::atoi(fe), ce && std::atoi(ce));
+        if (!p || r.route == HitRoute::Device) return;  // no sink: every hit goes after the pass
+        if (r.route == HitRoute::Expander) {
             if (!c->expander)
                 c->expander = std::make_unique<Expander>(c->device, hostThreads(c, 8) - 1, &c->place);
             c->expander->setStarts(&c->I.recStarts);
             c->expander->mark = [c](const char* w, uint64_t i) { c->mark(w, i); };
             c->expander->reset();
         }
+        sink = std::move(p);
+        c->sk.host = sink.get();
+        c->sk.cap = cap;
+        c->sk.route = r.route;
+        c->sk.wholeFallback = r.wholeFallback;
     }
-    const auto tC = clk::now();
-    run(c, false);
-    c->sk.limitN = 0;
-    uint32_t bad = 0;
-    SH_HIP(hipMemcpy(&bad, c->badFlag.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (bad) throw Error("pattern rank out of range for this index");
-    failed.dismiss();
-    c->sk.sink = nullptr;  // the pass is over; `sink` frees it should the expansion or the output fail
-    if (c->sk.compact) c->expander->drain();
-    c->mark("run end", 0);
-    c->sk.streaming = false;  // every chunk is up: sahara_gpu_run may re-run the staged patterns
-    c->stats.stage_ms = c->up.hostMs;
-    for (int b = 0; b < 3; ++b) c->stats.upload_chunks[b] = c->up.chunks[b];
-    const auto t0 = std::chrono::steady_clock::now();
-    if (hostLimit) {
-        std::vector<sahara_hit> v(c->nout);
-        if (c->nout) SH_HIP(hipMemcpy(v.data(), c->wholeHits(), c->nout * sizeof(sahara_hit), hipMemcpyDeviceToHost));
-        limitHits(v, max_hits);
-        handOver(v, hits, n_hits);
-    } else {
+
+    void collect(Ctx* c) {
+        if (hostLimit) {
+            std::vector<sahara_hit> v(c->nout);
+            if (c->nout) SH_HIP(hipMemcpy(v.data(), c->wholeHits(), c->nout * sizeof(sahara_hit), hipMemcpyDeviceToHost));
+            limitHits(v, maxHits);
+            return handOver(v, hits, nHits);
+        }
         if (sink && c->nout > c->sk.cap) sink.reset();  // more hits than the sink holds: a bigger buffer, copied whole
-        bool pinned = sink != nullptr && c->sk.pinned;
         if (!sink) {
             c->sk.done = 0;
             sink.reset(allocHits(c->nout, &pinned, nullptr, c->lastHits != 0));
@@ -801,219 +385,141 @@ static void searchStreamed(Ctx* c, const uint8_t* src, uint64_t rows, bool rc, u
             }
         }
         *hits = static_cast<sahara_hit*>(sink.release());
-        *n_hits = c->nout;
+        *nHits = c->nout;
     }
-    c->lastHits = c->nout;
-    c->stats.output_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (std::getenv("SAHARA_TIMING")) {  // where a call's wall time goes (stderr)
-        auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+
+    void timing(const Ctx* c, const CallTimes& t) const {  // where a call's wall time goes
         std::fprintf(stderr, "[sahara] stage %.1f ms, sink %.1f ms, pass %.1f ms (host packing %.1f ms), output %.1f ms\n",
-                     ms(tA, tB), ms(tB, tC), ms(tC, t0), c->up.hostMs, c->stats.output_ms);
-        traceEnd(c);
+                     msBetween(t.start, t.staged), msBetween(t.staged, t.sinkOpen), msBetween(t.sinkOpen, t.passDone),
+                     c->up.hostMs, c->stats.output_ms);
     }
-}
+};
 
-int sahara_gpu_search(void* ctx, const uint8_t* ranks, uint64_t n_patterns, uint32_t len, const uint32_t* pi,
-                      const uint32_t* l, const uint32_t* u, uint32_t n_searches, int edit, uint32_t max_hits,
-                      sahara_hit** hits, uint64_t* n_hits) {
-    return guarded([&] {
-        searchStreamed(ctxOf(ctx), ranks, n_patterns, false, n_patterns, len, Schemes{pi, l, u, &n_searches, 1, edit},
-                       max_hits, hits, n_hits);
-    });
-}
+// Records in blocks, returned as sahara_hit_blocks (the compact calls): every
+// batch's hits as 8-B records, copied by the device into a pinned host buffer
+// (pass.cpp sinkBatch), handed over as blocks (one per batch).
+struct BlockRecs {
+    sahara_hit_blocks* out;
+    HostBuf recs{nullptr, freeHits};
+    uint64_t recCap = 0;
 
-int sahara_gpu_search_reads(void* ctx, const uint8_t* reads, uint64_t n_reads, uint32_t len, int reverse,
-                            uint64_t limit, const uint32_t* pi, const uint32_t* l, const uint32_t* u,
-                            uint32_t n_searches, int edit, uint32_t max_hits, sahara_hit** hits, uint64_t* n_hits) {
-    return guarded([&] {
-        Ctx* c = ctxOf(ctx);
-        if (c->I.sigma != 5 && c->I.sigma != 6) throw Error("reverse complements need a dna4 or dna5 index");
-        const ReadRows R = readRows(reverse, n_reads, limit);
-        searchStreamed(c, reads, R.rows, reverse != 0, R.npat, len, Schemes{pi, l, u, &n_searches, 1, edit}, max_hits,
-                       hits, n_hits);
-    });
-}
-
-// sahara_gpu_search_reads_compact: the streamed pass with every batch's hits
-// written as 8-B records by the device into a pinned host sink (pass.cpp
-// finish), handed over as blocks (one per batch).
-static void searchReadsCompact(Ctx* c, const uint8_t* reads, uint64_t n_reads, uint32_t len, int reverse,
-                               uint64_t limit, const Schemes& sc, sahara_hit_blocks* out,
-                               const PackedReads* packed = nullptr) {
-    using clk = std::chrono::steady_clock;
-    const auto tA = clk::now();
-    if (c->I.sigma != 5 && c->I.sigma != 6) throw Error("reverse complements need a dna4 or dna5 index");
-    if (!c->more.empty()) throw Error("compact hit records need a single-part index (text < 2^32 symbols)");
-    const ReadRows R = readRows(reverse, n_reads, limit);
-    traceBegin(c, tA);
-    for (uint64_t i = 0, n = sc.rows() * len; i < n; ++i)  // before staging: a refused call stages nothing
-        if (sc.u[i] > 15) throw Error("compact hit records hold at most 15 errors");
-    HostBuf recs(nullptr, freeHits);
-    stageStreamed(c, reads, R.rows, reverse != 0, R.npat, len, sc.pi, sc.l, sc.u, sc.ns, sc.n, sc.edit, packed);
-    // (until the pass starts only the packing can be reading the caller's reads)
-    bool passStarted = false;
-    ScopeExit failed([&] { abandonCall(c, !passStarted); });
     // the sink, sized from the last call (else 2 hits per pattern), always
     // page-locked: the device writes into it
-    bool pinned = false;
-    size_t capBytes = 0;
-    recs.reset(allocPinned(sinkEstimate(c, R.npat) * 8, &pinned, &capBytes, true, true));
-    if (!recs) throw Error("out of host memory for hits");
-    c->sk.recs = true;
-    c->sk.blockRecs = pinned ? static_cast<uint64_t*>(recs.get()) : nullptr;
-    c->sk.cap = pinned ? capBytes / 8 : 0;
-    if (c->sk.cap) c->reserveRecs(c->sk.cap);
-    uint64_t recCap = capBytes / 8;
+    void openSink(Ctx* c, uint64_t npat) {
+        bool pinned = false;
+        size_t capBytes = 0;
+        recs.reset(allocPinned(sinkEstimate(c, npat) * 8, &pinned, &capBytes, true, true));
+        if (!recs) throw Error("out of host memory for hits");
+        c->sk.route = HitRoute::Records;
+        c->sk.host = pinned ? recs.get() : nullptr;
+        c->sk.cap = pinned ? capBytes / 8 : 0;
+        if (c->sk.cap) c->reserveRecs(c->sk.cap);
+        recCap = capBytes / 8;
+    }
+
+    void collect(Ctx* c) {
+        if (!c->sk.host || c->sk.done < c->nout) {
+            // the sink held too few (or is not pinned): the records of every
+            // batch again, from the device-resident records (c->outRecs holds the
+            // whole call's: pass.cpp finish), into one that fits
+            if (c->nout > recCap) {
+                bool pinned = false;
+                size_t capBytes = 0;
+                recs.reset();
+                recs.reset(allocPinned(c->nout * 8, &pinned, &capBytes, true, true));
+                if (!recs) throw Error("out of host memory for hits");
+            }
+            uint64_t b0 = 0;
+            for (size_t b = 0; b < c->batchQ0.size(); b0 = c->batchEnd[b], ++b)
+                if (!c->batchDirect[b])  // (a batch of 2^28 queries or more: whole hits in c->out)
+                    launchCompactHits(c->out.ptr + b0, c->batchEnd[b] - b0, c->batchQ0[b], c->I.dRecStarts.ptr,
+                                      c->outRecs.ptr + b0, c->st);
+            if (c->nout) SH_HIP(hipMemcpyAsync(recs.get(), c->outRecs.ptr, c->nout * 8, hipMemcpyDeviceToHost, c->st));
+            SH_HIP(hipStreamSynchronize(c->st));
+        }
+        const size_t nb = c->batchQ0.size();
+        HostBuf q0(std::malloc(std::max<size_t>(nb, 1) * 8), std::free);
+        HostBuf end(std::malloc(std::max<size_t>(nb, 1) * 8), std::free);
+        if (!q0 || !end) throw Error("out of host memory for hit blocks");
+        if (nb) std::memcpy(q0.get(), c->batchQ0.data(), nb * 8);
+        if (nb) std::memcpy(end.get(), c->batchEnd.data(), nb * 8);
+        if (c->recStartsEnd.size() != c->I.recStarts.size() + 1) {
+            c->recStartsEnd = c->I.recStarts;
+            c->recStartsEnd.push_back(c->I.n);
+        }
+        out->recs = static_cast<uint64_t*>(recs.release());
+        out->n_hits = c->nout;
+        out->block_qid0 = static_cast<uint64_t*>(q0.release());
+        out->block_end = static_cast<uint64_t*>(end.release());
+        out->n_blocks = nb;
+        out->rec_starts = c->recStartsEnd.data();
+        out->n_records = c->I.recStarts.size();
+    }
+
+    void timing(const Ctx* c, const CallTimes& t) const {
+        std::fprintf(stderr, "[sahara] compact call %.1f ms (host packing %.1f ms), output %.1f ms\n",
+                     msBetween(t.start, clk::now()), c->up.hostMs, c->stats.output_ms);
+    }
+};
+
+// Every streamed search call (search.cpp:218-250 from host queries to host
+// hits): the streamed upload, the pipelined pass with each batch's hits on
+// their way to the host while later batches search, then what is left of
+// them, in the shape `out` (declared by the caller, so that its buffer
+// outlives the guard here).
+template <typename Out>
+static void streamedCall(Ctx* c, const Queries& q, const Schemes& sc, Out& out) {
+    CallTimes t{};
+    t.start = clk::now();
+    traceBegin(c, t.start);
+    stageStreamed(c, q.src, q.rows, q.rc, q.npat, q.len, sc.pi, sc.l, sc.u, sc.ns, sc.n, sc.edit, q.packed);
+    // (until the pass starts only the packing can be reading the caller's queries)
+    bool passStarted = false;
+    ScopeExit failed([&] { abandonCall(c, !passStarted); });
+    t.staged = clk::now();
+    out.openSink(c, q.npat);
+    t.sinkOpen = clk::now();
     passStarted = true;
     run(c, false);
+    c->sk.limitN = 0;
     uint32_t bad = 0;
     SH_HIP(hipMemcpy(&bad, c->badFlag.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (bad) throw Error("pattern rank out of range for this index");
-    const auto t0 = clk::now();
-    if (!c->sk.blockRecs || c->sk.done < c->nout) {
-        // the sink held too few (or is not pinned): the records of every
-        // batch again, from the device-resident records (c->outRecs holds the
-        // whole call's: pass.cpp finish), into one that fits
-        if (c->nout > recCap) {
-            recs.reset();
-            recs.reset(allocPinned(c->nout * 8, &pinned, &capBytes, true, true));
-            if (!recs) throw Error("out of host memory for hits");
-            recCap = capBytes / 8;
-        }
-        uint64_t b0 = 0;
-        for (size_t b = 0; b < c->batchQ0.size(); b0 = c->batchEnd[b], ++b)
-            if (!c->batchDirect[b])  // (a batch of 2^28 queries or more: whole hits in c->out)
-                launchCompactHits(c->out.ptr + b0, c->batchEnd[b] - b0, c->batchQ0[b], c->I.dRecStarts.ptr,
-                                  c->outRecs.ptr + b0, c->st);
-        if (c->nout) SH_HIP(hipMemcpyAsync(recs.get(), c->outRecs.ptr, c->nout * 8, hipMemcpyDeviceToHost, c->st));
-        SH_HIP(hipStreamSynchronize(c->st));
-    }
-    c->stats.output_ms = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+    if (c->sk.route == HitRoute::Expander) c->expander->drain();
+    c->mark("run end", 0);
+    t.passDone = clk::now();
+    out.collect(c);
+    c->stats.output_ms = msBetween(t.passDone, clk::now());
     failed.dismiss();
-    c->sk.blockRecs = nullptr;
-    c->sk.recs = false;
-    c->sk.streaming = false;
+    c->sk.route = HitRoute::Device;  // the pass is over: the sink is the caller's
+    c->sk.wholeFallback = false;
+    c->sk.host = nullptr;
+    c->sk.streaming = false;  // every chunk is up: sahara_gpu_run may re-run the staged patterns
     c->stats.stage_ms = c->up.hostMs;
     for (int b = 0; b < 3; ++b) c->stats.upload_chunks[b] = c->up.chunks[b];
-    const size_t nb = c->batchQ0.size();
-    HostBuf q0(std::malloc(std::max<size_t>(nb, 1) * 8), std::free);
-    HostBuf end(std::malloc(std::max<size_t>(nb, 1) * 8), std::free);
-    if (!q0 || !end) throw Error("out of host memory for hit blocks");
-    if (nb) std::memcpy(q0.get(), c->batchQ0.data(), nb * 8);
-    if (nb) std::memcpy(end.get(), c->batchEnd.data(), nb * 8);
-    if (c->recStartsEnd.size() != c->I.recStarts.size() + 1) {
-        c->recStartsEnd = c->I.recStarts;
-        c->recStartsEnd.push_back(c->I.n);
-    }
-    out->recs = static_cast<uint64_t*>(recs.release());
-    out->n_hits = c->nout;
-    out->block_qid0 = static_cast<uint64_t*>(q0.release());
-    out->block_end = static_cast<uint64_t*>(end.release());
-    out->n_blocks = nb;
-    out->rec_starts = c->recStartsEnd.data();
-    out->n_records = c->I.recStarts.size();
     c->lastHits = c->nout;
     if (std::getenv("SAHARA_TIMING")) {
-        auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-        std::fprintf(stderr, "[sahara] compact call %.1f ms (host packing %.1f ms), output %.1f ms\n", ms(tA, clk::now()),
-                     c->up.hostMs, c->stats.output_ms);
+        out.timing(c, t);
         traceEnd(c);
     }
 }
 
-int sahara_gpu_search_reads_compact(void* ctx, const uint8_t* reads, uint64_t n_reads, uint32_t len, int reverse,
-                                    uint64_t limit, const uint32_t* pi, const uint32_t* l, const uint32_t* u,
-                                    uint32_t n_searches, int edit, sahara_hit_blocks* out) {
-    return guarded([&] {
-        if (!out) throw Error("sahara_gpu_search_reads_compact: null output");
-        *out = sahara_hit_blocks{};
-        searchReadsCompact(ctxOf(ctx), reads, n_reads, len, reverse, limit, Schemes{pi, l, u, &n_searches, 1, edit}, out);
-    });
+static void searchWhole(Ctx* c, const Queries& q, const Schemes& sc, uint32_t max_hits, sahara_hit** hits,
+                        uint64_t* n_hits) {
+    WholeHits out{max_hits, hits, n_hits};
+    streamedCall(c, q, sc, out);
 }
 
-int sahara_gpu_search_packed(void* ctx, const uint8_t* codes, uint64_t sym0, const uint64_t* n_pos, uint64_t n_count,
-                             uint64_t n_reads, uint32_t len, int reverse, uint64_t limit, const uint32_t* pi,
-                             const uint32_t* l, const uint32_t* u, uint32_t n_searches, int edit, uint32_t max_hits,
-                             sahara_hit** hits, uint64_t* n_hits) {
-    return guarded([&] {
-        Ctx* c = ctxOf(ctx);
-        if (!codes || (n_count && !n_pos)) throw Error("sahara_gpu_search_packed: null input");
-        const ReadRows R = readRows(reverse, n_reads, limit);
-        const PackedReads pk{sym0, n_pos, n_count};
-        searchStreamed(c, codes, R.rows, reverse != 0, R.npat, len, Schemes{pi, l, u, &n_searches, 1, edit}, max_hits,
-                       hits, n_hits, &pk);
-    });
-}
-
-int sahara_gpu_search_packed_compact(void* ctx, const uint8_t* codes, uint64_t sym0, const uint64_t* n_pos,
-                                     uint64_t n_count, uint64_t n_reads, uint32_t len, int reverse, uint64_t limit,
-                                     const uint32_t* pi, const uint32_t* l, const uint32_t* u, uint32_t n_searches,
-                                     int edit, sahara_hit_blocks* out) {
-    return guarded([&] {
-        if (!out) throw Error("sahara_gpu_search_packed_compact: null output");
-        *out = sahara_hit_blocks{};
-        if (!codes || (n_count && !n_pos)) throw Error("sahara_gpu_search_packed_compact: null input");
-        const PackedReads pk{sym0, n_pos, n_count};
-        searchReadsCompact(ctxOf(ctx), codes, n_reads, len, reverse, limit, Schemes{pi, l, u, &n_searches, 1, edit}, out,
-                           &pk);
-    });
-}
-
-int sahara_gpu_prepare(void* ctx, uint64_t n_patterns, uint32_t len) {
-    return guarded([&] {
-        if (n_patterns == 0) return;
-        Ctx* c = ctx ? ctxOf(ctx) : nullptr;
-        if (c) SH_HIP(hipSetDevice(c->device));
-        // the sink the first compact call asks the pool for (searchReadsCompact),
-        // pinned now and handed back to the pool, where the call finds it
-        const uint64_t est = sinkEstimate(c, n_patterns);
-        bool pinned = false;
-        size_t capBytes = 0;
-        {
-            HitPool& P = hitPool();
-            std::lock_guard<std::mutex> g(P.mu);
-            for (auto& e : P.idle)
-                if (e.second >= est * 8) {  // pinned already (a NULL-context call before)
-                    pinned = true;
-                    capBytes = e.second;
-                }
-        }
-        if (!pinned) {
-            void* p = allocPinned(est * 8, &pinned, &capBytes, true, true);
-            if (!p) throw Error("out of host memory for hits");
-            freeHits(p);
-        }
-        if (!c) return;  // (NULL context: the host part only, e.g. beside the index load)
-        if (pinned) c->reserveRecs(capBytes / 8);
-        c->out.reserve(est);
-        // the slots and the locate chain's buffers of a streamed pass, from
-        // the pass's own sizing (pass.cpp; the keys sized for a batch's rows
-        // at four per pattern, grown by the pass if short)
-        const PassKnobs k = readPassKnobs(c->verify);
-        const uint64_t maxBatch = maxBatchOf(std::nullopt, true, 1, false);
-        initWorkCaps(c, maxBatch, k);
-        const uint64_t nb = std::min<uint64_t>((n_patterns + maxBatch - 1) / maxBatch, Ctx::kSlots);
-        reserveLocate(c, maxBatch, nb);
-        c->partial.reserve(scanTiles((uint32_t)maxBatch));
-        c->k0.reserve(std::min<uint64_t>(n_patterns, maxBatch) * 4);
-        for (uint64_t i = 0; i < nb; ++i) reserveSlot(c, c->slot[i]);
-        if (len) {
-            const uint64_t patWords = (len + 7) / 8, patBlocks = (len + 31) / 32;
-            c->rawPats.reserve(n_patterns * len);
-            c->pats.reserve(n_patterns * patWords + 4);
-            c->pats3.reserve(n_patterns * patBlocks);
-            c->readRaw.reserve((n_patterns + 1) / 2 * len);
-            c->nibPats.reserve((n_patterns * len + 1) / 2 + 16);  // the streamed upload's staging (staging.cpp)
-        }
-    });
-}
-
-void sahara_gpu_free_blocks(sahara_hit_blocks* b) {
-    if (!b) return;
-    freeHits(b->recs);
-    std::free(b->block_qid0);
-    std::free(b->block_end);
-    *b = sahara_hit_blocks{};
+// The compact calls refuse before staging: a refused call stages nothing.
+static void searchBlocks(Ctx* c, const uint8_t* reads, uint64_t n_reads, uint32_t len, int reverse, uint64_t limit,
+                         const Schemes& sc, sahara_hit_blocks* blocks, const PackedReads* packed = nullptr) {
+    if (c->I.sigma != 5 && c->I.sigma != 6) throw Error("reverse complements need a dna4 or dna5 index");
+    if (!c->more.empty()) throw Error("compact hit records need a single-part index (text < 2^32 symbols)");
+    const ReadRows R = readRows(reverse, n_reads, limit);
+    for (uint64_t i = 0, n = sc.rows() * len; i < n; ++i)
+        if (sc.u[i] > 15) throw Error("compact hit records hold at most 15 errors");
+    BlockRecs out{blocks};
+    streamedCall(c, Queries{reads, R.rows, reverse != 0, R.npat, len, packed}, sc, out);
 }
 
 // besthits on the host: a loop over the exact-j schemes, each a whole
@@ -1121,11 +627,177 @@ static void bestStreamed(Ctx* c, const uint8_t* src, uint64_t n_reads, uint32_t 
     if (c->more.empty() && !bestHostForced()) {
         if (interleave && !packed && c->I.sigma != 5 && c->I.sigma != 6)
             throw Error("reverse complements need a dna4 or dna5 index");
-        return searchStreamed(c, src, R.rows, rc, R.npat, len, sc, max_hits, hits, n_hits, packed);
+        return searchWhole(c, Queries{src, R.rows, rc, R.npat, len, packed}, sc, max_hits, hits, n_hits);
     }
     if (!interleave) return bestOnHost(c, src, R.npat, len, sc, max_hits, hits, n_hits);
     const std::vector<uint8_t> ranks = queryRanks(c, src, len, rc, R, packed);
     bestOnHost(c, ranks.data(), R.npat, len, sc, max_hits, hits, n_hits);
+}
+
+}  // namespace sahara
+
+extern "C" {
+
+int sahara_gpu_stage(void* ctx, const uint8_t* ranks, uint64_t n_patterns, uint32_t len, const uint32_t* pi,
+                     const uint32_t* l, const uint32_t* u, uint32_t n_searches, int edit) {
+    return guarded([&] { stage(ctxOf(ctx), ranks, n_patterns, len, pi, l, u, &n_searches, 1, edit); });
+}
+
+int sahara_gpu_run(void* ctx, int count, uint64_t* n_hits) {
+    return guarded([&] {
+        Ctx* c = ctxOf(ctx);
+        traceBegin(c, std::chrono::steady_clock::now());
+        run(c, count != 0);
+        if (n_hits) *n_hits = c->nout;
+        if (c->traceOn) {
+            c->mark("run returns", 0);
+            std::sort(c->trace.begin(), c->trace.end());
+            for (auto& m : c->trace) std::fprintf(stderr, "[sahara]   %8.3f %s\n", m.first, m.second.c_str());
+            c->traceOn = false;
+        }
+    });
+}
+
+int sahara_gpu_fetch(void* ctx, sahara_hit* out, uint64_t capacity, uint64_t* n_hits) {
+    return guarded([&] {
+        Ctx* c = ctxOf(ctx);
+        if (n_hits) *n_hits = c->nout;
+        if (capacity < c->nout) throw Error("sahara_gpu_fetch: capacity too small");
+        if (c->nout) SH_HIP(hipMemcpy(out, c->wholeHits(), c->nout * sizeof(sahara_hit), hipMemcpyDeviceToHost));
+    });
+}
+
+int sahara_gpu_copy_hits(void* ctx, void* dst_device, uint64_t capacity, uint64_t qid_offset, uint64_t* n_hits) {
+    return guarded([&] {
+        Ctx* c = ctxOf(ctx);
+        if (n_hits) *n_hits = c->nout;
+        if (capacity < c->nout) throw Error("sahara_gpu_copy_hits: capacity too small");
+        if (c->nout && !dst_device) throw Error("sahara_gpu_copy_hits: null destination");
+        launchCopyHits(c->wholeHits(), c->nout, qid_offset, static_cast<sahara_hit*>(dst_device), c->st);
+        SH_HIP(hipStreamSynchronize(c->st));
+    });
+}
+
+int sahara_gpu_digest(void* ctx, uint64_t* digest) {
+    return guarded([&] {
+        Ctx* c = ctxOf(ctx);
+        SH_HIP(hipMemsetAsync(c->counters.ptr + 4, 0, 8, c->st));
+        launchDigest(c->wholeHits(), c->nout, c->counters.ptr + 4, c->st);
+        unsigned long long d = 0;
+        SH_HIP(hipMemcpyAsync(&d, c->counters.ptr + 4, 8, hipMemcpyDeviceToHost, c->st));
+        SH_HIP(hipStreamSynchronize(c->st));
+        *digest = d;
+    });
+}
+
+int sahara_gpu_stats(void* ctx, sahara_stats* stats) {
+    return guarded([&] { *stats = ctxOf(ctx)->stats; });
+}
+
+int sahara_gpu_search(void* ctx, const uint8_t* ranks, uint64_t n_patterns, uint32_t len, const uint32_t* pi,
+                      const uint32_t* l, const uint32_t* u, uint32_t n_searches, int edit, uint32_t max_hits,
+                      sahara_hit** hits, uint64_t* n_hits) {
+    return guarded([&] {
+        searchWhole(ctxOf(ctx), Queries{ranks, n_patterns, false, n_patterns, len, nullptr},
+                    Schemes{pi, l, u, &n_searches, 1, edit}, max_hits, hits, n_hits);
+    });
+}
+
+int sahara_gpu_search_reads(void* ctx, const uint8_t* reads, uint64_t n_reads, uint32_t len, int reverse,
+                            uint64_t limit, const uint32_t* pi, const uint32_t* l, const uint32_t* u,
+                            uint32_t n_searches, int edit, uint32_t max_hits, sahara_hit** hits, uint64_t* n_hits) {
+    return guarded([&] {
+        Ctx* c = ctxOf(ctx);
+        if (c->I.sigma != 5 && c->I.sigma != 6) throw Error("reverse complements need a dna4 or dna5 index");
+        const ReadRows R = readRows(reverse, n_reads, limit);
+        searchWhole(c, Queries{reads, R.rows, reverse != 0, R.npat, len, nullptr}, Schemes{pi, l, u, &n_searches, 1, edit},
+                    max_hits, hits, n_hits);
+    });
+}
+
+int sahara_gpu_search_reads_compact(void* ctx, const uint8_t* reads, uint64_t n_reads, uint32_t len, int reverse,
+                                    uint64_t limit, const uint32_t* pi, const uint32_t* l, const uint32_t* u,
+                                    uint32_t n_searches, int edit, sahara_hit_blocks* out) {
+    return guarded([&] {
+        if (!out) throw Error("sahara_gpu_search_reads_compact: null output");
+        *out = sahara_hit_blocks{};
+        searchBlocks(ctxOf(ctx), reads, n_reads, len, reverse, limit, Schemes{pi, l, u, &n_searches, 1, edit}, out);
+    });
+}
+
+int sahara_gpu_search_packed(void* ctx, const uint8_t* codes, uint64_t sym0, const uint64_t* n_pos, uint64_t n_count,
+                             uint64_t n_reads, uint32_t len, int reverse, uint64_t limit, const uint32_t* pi,
+                             const uint32_t* l, const uint32_t* u, uint32_t n_searches, int edit, uint32_t max_hits,
+                             sahara_hit** hits, uint64_t* n_hits) {
+    return guarded([&] {
+        Ctx* c = ctxOf(ctx);
+        if (!codes || (n_count && !n_pos)) throw Error("sahara_gpu_search_packed: null input");
+        const ReadRows R = readRows(reverse, n_reads, limit);
+        const PackedReads pk{sym0, n_pos, n_count};
+        searchWhole(c, Queries{codes, R.rows, reverse != 0, R.npat, len, &pk}, Schemes{pi, l, u, &n_searches, 1, edit},
+                    max_hits, hits, n_hits);
+    });
+}
+
+int sahara_gpu_search_packed_compact(void* ctx, const uint8_t* codes, uint64_t sym0, const uint64_t* n_pos,
+                                     uint64_t n_count, uint64_t n_reads, uint32_t len, int reverse, uint64_t limit,
+                                     const uint32_t* pi, const uint32_t* l, const uint32_t* u, uint32_t n_searches,
+                                     int edit, sahara_hit_blocks* out) {
+    return guarded([&] {
+        if (!out) throw Error("sahara_gpu_search_packed_compact: null output");
+        *out = sahara_hit_blocks{};
+        if (!codes || (n_count && !n_pos)) throw Error("sahara_gpu_search_packed_compact: null input");
+        const PackedReads pk{sym0, n_pos, n_count};
+        searchBlocks(ctxOf(ctx), codes, n_reads, len, reverse, limit, Schemes{pi, l, u, &n_searches, 1, edit}, out, &pk);
+    });
+}
+
+int sahara_gpu_prepare(void* ctx, uint64_t n_patterns, uint32_t len) {
+    return guarded([&] {
+        if (n_patterns == 0) return;
+        Ctx* c = ctx ? ctxOf(ctx) : nullptr;
+        if (c) SH_HIP(hipSetDevice(c->device));
+        // the sink the first compact call asks the pool for (BlockRecs::openSink),
+        // pinned now and handed back to the pool, where the call finds it
+        const uint64_t est = sinkEstimate(c, n_patterns);
+        size_t capBytes = hitPool().idleHolding(est * 8);  // pinned already (a NULL-context call before)
+        bool pinned = capBytes != 0;
+        if (!pinned) {
+            void* p = allocPinned(est * 8, &pinned, &capBytes, true, true);
+            if (!p) throw Error("out of host memory for hits");
+            freeHits(p);
+        }
+        if (!c) return;  // (NULL context: the host part only, e.g. beside the index load)
+        if (pinned) c->reserveRecs(capBytes / 8);
+        c->out.reserve(est);
+        // the slots and the locate chain's buffers of a streamed pass, from
+        // the pass's own sizing (pass.cpp; the keys sized for a batch's rows
+        // at four per pattern, grown by the pass if short)
+        const PassKnobs k = readPassKnobs(c->verify);
+        const uint64_t maxBatch = maxBatchOf(std::nullopt, true, 1, false);
+        initWorkCaps(c, maxBatch, k);
+        const uint64_t nb = std::min<uint64_t>((n_patterns + maxBatch - 1) / maxBatch, Ctx::kSlots);
+        reserveLocate(c, maxBatch, nb);
+        c->partial.reserve(scanTiles((uint32_t)maxBatch));
+        c->k0.reserve(std::min<uint64_t>(n_patterns, maxBatch) * 4);
+        for (uint64_t i = 0; i < nb; ++i) reserveSlot(c, c->slot[i]);
+        if (len) {
+            const uint64_t patWords = (len + 7) / 8, patBlocks = (len + 31) / 32;
+            c->rawPats.reserve(n_patterns * len);
+            c->pats.reserve(n_patterns * patWords + 4);
+            c->pats3.reserve(n_patterns * patBlocks);
+            c->readRaw.reserve((n_patterns + 1) / 2 * len);
+            c->nibPats.reserve((n_patterns * len + 1) / 2 + 16);  // the streamed upload's staging (staging.cpp)
+        }
+    });
+}
+
+void sahara_gpu_free_blocks(sahara_hit_blocks* b) {
+    if (!b) return;
+    freeHits(b->recs);
+    std::free(b->block_qid0);
+    std::free(b->block_end);
+    *b = sahara_hit_blocks{};
 }
 
 int sahara_gpu_search_best(void* ctx, const uint8_t* ranks, uint64_t n_patterns, uint32_t len, const uint32_t* pi,
@@ -1176,309 +848,8 @@ int sahara_gpu_search_best_packed_compact(void* ctx, const uint8_t* codes, uint6
         if (!codes || (n_count && !n_pos)) throw Error("sahara_gpu_search_best_packed_compact: null input");
         if (!n_schemes) throw Error("besthits: no schemes");
         const PackedReads pk{sym0, n_pos, n_count};
-        searchReadsCompact(c, codes, n_reads, len, reverse, limit, Schemes{pi, l, u, n_searches, n_schemes, 1}, out, &pk);
+        searchBlocks(c, codes, n_reads, len, reverse, limit, Schemes{pi, l, u, n_searches, n_schemes, 1}, out, &pk);
     });
-}
-
-// ------------------------------------------------------------ alignment ----
-// sahara_gpu_align[_packed_compact]: the call's patterns staged whole as
-// 3-bit-plane blocks, then the hit records up and the alignment records down
-// chunk by chunk on stream st, kAlignHits between (align.hip). Every hit is
-// checked on the host before anything is staged: a refused call launches
-// nothing and leaves `out` alone.
-
-static void checkAlignBounds(uint32_t len, uint32_t max_err) {
-    if (max_err > SAHARA_ALIGN_MAX_ERR)
-        throw Error("alignment: max_err above SAHARA_ALIGN_MAX_ERR (" + std::to_string(SAHARA_ALIGN_MAX_ERR) + ")");
-    if (len == 0 || len > 16383) throw Error("alignment: pattern length out of range (1..16383)");
-}
-
-static uint64_t alignChunk() {
-    const char* e = std::getenv("SAHARA_ALIGN_CHUNK");
-    const long long v = e ? std::atoll(e) : 0;
-    return v > 0 ? std::min<uint64_t>((uint64_t)v, 1ull << 28) : 1ull << 22;
-}
-
-// f(a, b) over [0, n) in slices, on up to 8 threads (the checks of tens of millions of hit records)
-static void alignSlices(uint64_t n, const std::function<void(uint64_t, uint64_t)>& f) {
-    const unsigned nt = n < (1u << 20) ? 1 : std::max(1u, std::min(8u, std::thread::hardware_concurrency()));
-    if (nt == 1) return f((uint64_t)0, n);
-    const uint64_t per = (n + nt - 1) / nt;
-    std::vector<std::thread> ts;
-    for (unsigned t = 0; t < nt; ++t) {
-        const uint64_t a = std::min(n, t * per), b = std::min(n, a + per);
-        if (a < b) ts.emplace_back([&f, a, b] { f(a, b); });
-    }
-    for (auto& t : ts) t.join();
-}
-
-// the patterns [0, npat) of rank bytes -> c->align.pats3
-static void alignStageRanks(Ctx* c, const uint8_t* ranks, uint64_t npat, uint32_t m, uint32_t patBlocks) {
-    Ctx::Align& A = c->align;
-    A.pats3.reserve(npat * patBlocks + 1);
-    const uint64_t rowsPer = std::max<uint64_t>(1, (64ull << 20) / m);
-    A.raw.reserve(std::min(npat, rowsPer) * m);
-    for (uint64_t r0 = 0; r0 < npat; r0 += rowsPer) {
-        const uint64_t rows = std::min(rowsPer, npat - r0);
-        SH_HIP(hipMemcpyAsync(A.raw.ptr, ranks + r0 * m, rows * m, hipMemcpyHostToDevice, c->st));
-        launchPackPatterns3(A.raw.ptr, rows, m, patBlocks, A.pats3.ptr + r0 * patBlocks, c->st);
-        SH_HIP(hipStreamSynchronize(c->st));  // (raw is reused)
-    }
-}
-
-// the query list of a packed-reads call (R, as the search call forms it) -> c->align.pats3
-static void alignStagePacked(Ctx* c, const uint8_t* codes, const PackedReads& pk, const ReadRows& R, bool rc,
-                             uint32_t m, uint32_t patBlocks) {
-    Ctx::Align& A = c->align;
-    if (c->I.sigma != 5 && c->I.sigma != 6) throw Error("reads two bits per symbol need a dna4 or dna5 index");
-    const uint32_t patWords = (m + 7) / 8;
-    A.pats3.reserve(R.npat * patBlocks + 1);
-    A.pats4.reserve(R.npat * patWords);
-    const uint64_t lo = pk.sym0, hi = pk.sym0 + R.rows * m;
-    const uint64_t* nb = pk.nCount ? std::lower_bound(pk.nPos, pk.nPos + pk.nCount, lo) : nullptr;
-    const uint64_t* ne = pk.nCount ? std::lower_bound(nb, pk.nPos + pk.nCount, hi) : nullptr;
-    for (const uint64_t* q = nb; q && q < ne; ++q)
-        if (*q < lo || *q >= hi || (q > nb && *q <= q[-1]))
-            throw Error("N positions of packed reads must be strictly ascending");
-    if (nb != ne && c->I.sigma == 5) throw Error("pattern rank out of range for this index");
-    // chunks of whole reads, an even number each (a read and its reverse
-    // complement are patterns of one chunk), < 2^30 symbols: N positions
-    // relative to the chunk's first byte fit 32 bits
-    uint64_t rowsPer = std::max<uint64_t>(2, ((1ull << 28) / m) & ~1ull);
-    A.raw.reserve((std::min(R.rows, rowsPer) * m + 3) / 4 + 64);  // (a chunk's bytes start up to 4 early)
-    std::vector<uint32_t> rel;
-    for (uint64_t r0 = 0; r0 < R.rows; r0 += rowsPer) {
-        const uint64_t r1 = std::min(R.rows, r0 + rowsPer);
-        const uint64_t S0 = lo + r0 * m, S1 = lo + r1 * m;
-        const uint64_t B0 = (S0 / 4) & ~uint64_t(3), B1 = (S1 + 3) / 4;  // the chunk's bytes, from a whole word on
-        SH_HIP(hipMemsetAsync(A.raw.ptr + (B1 - B0), 0, 32, c->st));    // (kPackFrom2 reads three words per block)
-        SH_HIP(hipMemcpyAsync(A.raw.ptr, codes + B0, B1 - B0, hipMemcpyHostToDevice, c->st));
-        rel.clear();
-        for (; nb && nb < ne && *nb < S1; ++nb) rel.push_back((uint32_t)(*nb - 4 * B0));
-        A.nList.reserve(std::max<size_t>(rel.size(), 1));
-        if (!rel.empty())
-            SH_HIP(hipMemcpyAsync(A.nList.ptr, rel.data(), rel.size() * 4, hipMemcpyHostToDevice, c->st));
-        const uint64_t p0 = rc ? 2 * r0 : r0, p1 = rc ? std::min(2 * r1, R.npat) : r1;
-        launchPackFrom2(A.raw.ptr, (uint32_t)(S0 - 4 * B0), A.nList.ptr, (uint32_t)rel.size(), r0, p0, p1, m, rc,
-                        c->I.sigma, patWords, patBlocks, A.pats4.ptr, A.pats3.ptr, c->st);
-        SH_HIP(hipStreamSynchronize(c->st));  // (raw, nList and rel are reused)
-    }
-}
-
-// The chunk loop. recSize: bytes of a hit record (24 whole, 8 compact).
-static void alignChunks(Ctx* c, AlignArgs a, const void* hits, size_t recSize, uint64_t n_hits, sahara_alignment* out,
-                        double& kernelMs, uint64_t& chunks) {
-    Ctx::Align& A = c->align;
-    const uint64_t per = alignChunk();
-    A.in.reserve(std::min(per, n_hits) * recSize);
-    A.out.reserve(std::min(per, n_hits));
-    const Event e0(hipEventDefault), e1(hipEventDefault);
-    const bool whole = recSize == sizeof(sahara_hit);
-    for (uint64_t i0 = 0; i0 < n_hits; i0 += per, ++chunks) {
-        const uint64_t n = std::min(per, n_hits - i0);
-        SH_HIP(hipMemcpyAsync(A.in.ptr, static_cast<const char*>(hits) + i0 * recSize, n * recSize,
-                              hipMemcpyHostToDevice, c->st));
-        a.nHits = n;
-        a.first = i0;
-        a.out = A.out.ptr;
-        if (whole) a.hits = reinterpret_cast<const sahara_hit*>(A.in.ptr);
-        else a.recs = reinterpret_cast<const uint64_t*>(A.in.ptr);
-        SH_HIP(hipEventRecord(e0, c->st));
-        for (uint32_t p = 0; p <= c->more.size(); ++p) {  // every hit's record is of exactly one part
-            const DeviceIndex& I = partOf(c, p);
-            a.text3 = I.text3.ptr;
-            a.text3Bytes = (uint32_t)std::min<uint64_t>(text3Blocks(I.n) * 16, 0xFFFFFF00ull);
-            a.recStarts = I.dRecStarts.ptr;
-            a.rec0 = c->partRec0[p];
-            a.nrec = I.recLens.size();
-            launchAlignHits(a, c->st);
-        }
-        SH_HIP(hipEventRecord(e1, c->st));
-        SH_HIP(hipStreamSynchronize(c->st));  // (copyOut's small copies are not on st)
-        copyOut(c, out + i0, A.out.ptr, n * sizeof(sahara_alignment));
-        SH_HIP(hipStreamSynchronize(c->st));
-        float ms = 0;
-        SH_HIP(hipEventElapsedTime(&ms, e0, e1));
-        kernelMs += ms;
-    }
-}
-
-int sahara_gpu_align(void* ctx, const uint8_t* ranks, uint64_t n_patterns, uint32_t len, int edit, uint32_t max_err,
-                     const sahara_hit* hits, uint64_t n_hits, sahara_alignment* out) {
-    return guarded([&] {
-        using clk = std::chrono::steady_clock;
-        const auto t0 = clk::now();
-        Ctx* c = ctxOf(ctx);
-        checkAlignBounds(len, max_err);
-        if (n_hits && (!hits || !out || !ranks)) throw Error("sahara_gpu_align: null input");
-        // the hit records alone, before any address is formed from them
-        std::vector<const std::vector<uint64_t>*> lens;  // per part
-        for (uint32_t p = 0; p <= c->more.size(); ++p) lens.push_back(&partOf(c, p).recLens);
-        const uint64_t nrec = c->partRec0.back() + lens.back()->size();
-        std::atomic<uint64_t> firstBad{UINT64_MAX};  // the first hit that fails a check
-        alignSlices(n_hits, [&](uint64_t a, uint64_t b) {
-            uint32_t part = 0;
-            for (uint64_t i = a; i < b; ++i) {
-                const sahara_hit& h = hits[i];
-                bool ok = h.qid < n_patterns && h.seq_id < nrec;
-                if (ok) {
-                    if (h.seq_id < c->partRec0[part] || h.seq_id - c->partRec0[part] >= lens[part]->size())
-                        part = (uint32_t)(std::upper_bound(c->partRec0.begin(), c->partRec0.end(),
-                                                           (uint64_t)h.seq_id) - c->partRec0.begin() - 1);
-                    ok = h.pos < (*lens[part])[h.seq_id - c->partRec0[part]];
-                }
-                if (!ok) {
-                    uint64_t seen = firstBad.load();
-                    while (i < seen && !firstBad.compare_exchange_weak(seen, i)) {}
-                    return;
-                }
-            }
-        });
-        if (const uint64_t i = firstBad.load(); i != UINT64_MAX) {
-            const sahara_hit& h = hits[i];
-            if (h.qid >= n_patterns)
-                throw Error("sahara_gpu_align: hit " + std::to_string(i) + " names pattern " + std::to_string(h.qid) +
-                            " of " + std::to_string(n_patterns));
-            if (h.seq_id >= nrec)
-                throw Error("sahara_gpu_align: hit " + std::to_string(i) + " names record " +
-                            std::to_string(h.seq_id) + " of " + std::to_string(nrec));
-            throw Error("sahara_gpu_align: hit " + std::to_string(i) + " lies at position " + std::to_string(h.pos) +
-                        " outside record " + std::to_string(h.seq_id));
-        }
-        sahara_align_stats S{};
-        if (n_hits) {
-            const uint32_t patBlocks = (len + 31) / 32;
-            alignStageRanks(c, ranks, n_patterns, len, patBlocks);
-            S.stage_ms = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
-            AlignArgs a{};
-            a.pats3 = c->align.pats3.ptr;
-            a.patBlocks = patBlocks;
-            a.m = len;
-            a.maxErr = max_err;
-            a.edit = edit != 0;
-            alignChunks(c, a, hits, sizeof(sahara_hit), n_hits, out, S.kernel_ms, S.chunks);
-        }
-        S.hits = n_hits;
-        S.total_ms = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
-        c->align.stats = S;
-    });
-}
-
-int sahara_gpu_align_packed_compact(void* ctx, const uint8_t* codes, uint64_t sym0, const uint64_t* n_pos,
-                                    uint64_t n_count, uint64_t n_reads, uint32_t len, int reverse, uint64_t limit,
-                                    int edit, uint32_t max_err, const sahara_hit_blocks* blocks, sahara_alignment* out) {
-    return guarded([&] {
-        using clk = std::chrono::steady_clock;
-        const auto t0 = clk::now();
-        Ctx* c = ctxOf(ctx);
-        checkAlignBounds(len, max_err);
-        if (!c->more.empty()) throw Error("compact hit records need a single-part index (text < 2^32 symbols)");
-        if (!blocks || !codes || (n_count && !n_pos)) throw Error("sahara_gpu_align_packed_compact: null input");
-        const ReadRows R = readRows(reverse, n_reads, limit);
-        const uint64_t n_hits = blocks->n_hits;
-        if (n_hits && (!blocks->recs || !blocks->block_end || !blocks->block_qid0 || !blocks->n_blocks || !out))
-            throw Error("sahara_gpu_align_packed_compact: null input");
-        if (blocks->n_blocks > 0xFFFFFFFFull) throw Error("sahara_gpu_align_packed_compact: too many blocks");
-        // the records alone: blocks in order and covering them, every qid a pattern, every position in the text
-        uint64_t covered = 0;
-        for (uint64_t b = 0; n_hits && b < blocks->n_blocks; ++b) {
-            if (blocks->block_end[b] < covered || blocks->block_end[b] > n_hits)
-                throw Error("sahara_gpu_align_packed_compact: block ends out of order");
-            covered = blocks->block_end[b];
-        }
-        if (covered != n_hits) throw Error("sahara_gpu_align_packed_compact: the blocks do not cover the records");
-        std::atomic<uint64_t> firstBad{UINT64_MAX};
-        alignSlices(n_hits, [&](uint64_t a, uint64_t b) {
-            const uint64_t* ends = blocks->block_end;
-            uint64_t blk = (uint64_t)(std::upper_bound(ends, ends + blocks->n_blocks, a) - ends);
-            for (uint64_t i = a; i < b; ++i) {
-                while (i >= ends[blk]) ++blk;
-                const uint64_t v = blocks->recs[i], q0 = blocks->block_qid0[blk];
-                if (q0 >= R.npat || (v >> 36) >= R.npat - q0 || ((v >> 4) & 0xFFFFFFFFull) >= c->I.n) {
-                    uint64_t seen = firstBad.load();
-                    while (i < seen && !firstBad.compare_exchange_weak(seen, i)) {}
-                    return;
-                }
-            }
-        });
-        if (const uint64_t i = firstBad.load(); i != UINT64_MAX) {
-            if (((blocks->recs[i] >> 4) & 0xFFFFFFFFull) >= c->I.n)
-                throw Error("sahara_gpu_align_packed_compact: record " + std::to_string(i) + " lies outside the text");
-            throw Error("sahara_gpu_align_packed_compact: record " + std::to_string(i) +
-                        " names a pattern beyond the " + std::to_string(R.npat) + " of the call");
-        }
-        sahara_align_stats S{};
-        if (n_hits) {
-            const uint32_t patBlocks = (len + 31) / 32;
-            const PackedReads pk{sym0, n_pos, n_count};
-            alignStagePacked(c, codes, pk, R, reverse != 0, len, patBlocks);
-            Ctx::Align& A = c->align;
-            const uint64_t nb = blocks->n_blocks;
-            A.blocks.reserve(2 * nb);
-            SH_HIP(hipMemcpyAsync(A.blocks.ptr, blocks->block_end, nb * 8, hipMemcpyHostToDevice, c->st));
-            SH_HIP(hipMemcpyAsync(A.blocks.ptr + nb, blocks->block_qid0, nb * 8, hipMemcpyHostToDevice, c->st));
-            SH_HIP(hipStreamSynchronize(c->st));
-            S.stage_ms = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
-            AlignArgs a{};
-            a.pats3 = A.pats3.ptr;
-            a.patBlocks = patBlocks;
-            a.m = len;
-            a.maxErr = max_err;
-            a.edit = edit != 0;
-            a.blockEnd = A.blocks.ptr;
-            a.blockQid0 = A.blocks.ptr + nb;
-            a.nBlocks = (uint32_t)nb;
-            alignChunks(c, a, blocks->recs, 8, n_hits, out, S.kernel_ms, S.chunks);
-        }
-        S.hits = n_hits;
-        S.total_ms = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
-        c->align.stats = S;
-    });
-}
-
-int sahara_gpu_align_stats(void* ctx, sahara_align_stats* stats) {
-    return guarded([&] {
-        Ctx* c = ctxOf(ctx);
-        if (!stats) throw Error("sahara_gpu_align_stats: null output");
-        *stats = c->align.stats;
-    });
-}
-
-int sahara_cigar(const sahara_alignment* a, uint32_t len, char* buf, size_t cap) {
-    if (!a || !buf || a->err == SAHARA_ALIGN_NONE || a->err > SAHARA_ALIGN_MAX_ERR) return -1;
-    size_t at = 0;
-    char op = 0;
-    uint64_t run = 0;
-    bool full = false;
-    auto flush = [&] {
-        if (!run) return;
-        char tmp[24];
-        const int k = std::snprintf(tmp, sizeof tmp, "%llu%c", (unsigned long long)run, op);
-        if (at + (size_t)k + 1 > cap) full = true;
-        else std::memcpy(buf + at, tmp, (size_t)k), at += (size_t)k;
-        run = 0;
-    };
-    auto put = [&](char o, uint64_t n) {
-        if (!n) return;
-        if (o != op) flush();
-        op = o;
-        run += n;
-    };
-    uint32_t i = 0;  // pattern symbols written so far
-    for (uint32_t s = 0; s < a->err; ++s) {
-        const uint32_t qpos = a->edit[s] >> 2, kind = a->edit[s] & 3u;
-        if (qpos < i || qpos > len || kind == 0) return -1;
-        put('=', qpos - i);
-        i = qpos;
-        put(kind == 1 ? 'X' : kind == 2 ? 'I' : 'D', 1);
-        if (kind != 3) ++i;
-    }
-    if (i > len) return -1;
-    put('=', len - i);
-    flush();
-    if (full || at + 1 > cap) return -1;
-    buf[at] = 0;
-    return (int)at;
 }
 
 void sahara_gpu_free(void* p) { freeHits(p); }
@@ -1495,85 +866,6 @@ void* sahara_host_alloc(size_t bytes) {
 
 void sahara_host_free(void* p) {
     if (p) (void)hipHostFree(p);
-}
-
-void sahara_gpu_close(void* ctx) {
-    if (!ctx) return;
-    Ctx* c = static_cast<Ctx*>(ctx);
-    (void)hipSetDevice(c->device);
-    delete c;
-}
-
-// ------------------------------------------------------------ synthetic ----
-
-int sahara_synth_reference(uint64_t seed, uint32_t sigma, const uint64_t* rec_lens, uint64_t n_records,
-                           uint8_t* out) {
-    return guarded([&] {
-        if (sigma != 5 && sigma != 6) throw Error("sigma must be 5 or 6");
-        const uint8_t code[4] = {1, 2, 3, (uint8_t)(sigma == 6 ? 5 : 4)};
-        uint64_t total = 0;
-        for (uint64_t r = 0; r < n_records; ++r) total += rec_lens[r];
-        std::mt19937_64 gen(seed);
-        uint64_t i = 0;
-        for (; i + 32 <= total; i += 32) {
-            uint64_t x = gen();
-            for (int j = 0; j < 32; ++j) out[i + j] = code[(x >> (2 * j)) & 3u];
-        }
-        if (i < total) {
-            uint64_t x = gen();
-            for (int j = 0; i < total; ++i, ++j) out[i] = code[(x >> (2 * j)) & 3u];
-        }
-    });
-}
-
-int sahara_synth_reads(const uint8_t* ranks, const uint64_t* rec_lens, uint64_t n_records, uint32_t sigma,
-                       uint64_t n_reads, uint32_t len, uint32_t errors, uint64_t seed, uint8_t* out,
-                       uint64_t* origin) {
-    return guarded([&] { synthReads(ranks, rec_lens, n_records, sigma, n_reads, len, 0, 0, 0, errors, seed, out, origin); });
-}
-
-int sahara_synth_reads_typed(const uint8_t* ranks, const uint64_t* rec_lens, uint64_t n_records, uint32_t sigma,
-                             uint64_t n_reads, uint32_t len, uint32_t substitutions, uint32_t insertions,
-                             uint32_t deletions, uint32_t errors, uint64_t seed, uint8_t* out, uint64_t* origin) {
-    return guarded([&] {
-        synthReads(ranks, rec_lens, n_records, sigma, n_reads, len, substitutions, insertions, deletions, errors, seed,
-                   out, origin);
-    });
-}
-
-int sahara_pack_2bit(const uint8_t* ranks, uint64_t n, uint32_t sigma, int scalar, uint8_t* out, uint32_t* n_pos,
-                     uint64_t pos_cap, uint64_t* n_count) {
-    int bad = 0;
-    const int rc = guarded([&] {
-        if (sigma != 5 && sigma != 6) throw Error("sigma must be 5 or 6");
-        if (n >= (1ull << 32)) throw Error("at most 2^32 - 1 symbols per chunk");
-        std::vector<uint32_t> pos;
-        // scalar: 0 the widest the host has (AVX-512 / AVX2), 1 scalar, 2 AVX2 at most
-        const uint64_t acc = scalar == 1 ? pack2Scalar(ranks, out, n, sigma, 0, pos)
-                             : scalar == 2 ? (hostHasAvx2() ? pack2Avx2(ranks, out, n, sigma, 0, pos)
-                                                            : pack2Scalar(ranks, out, n, sigma, 0, pos))
-                                           : pack2Best(ranks, out, n, sigma, 0, pos);
-        bad = acc ? 1 : 0;
-        *n_count = pos.size();
-        if (n_pos && !pos.empty()) std::memcpy(n_pos, pos.data(), std::min<uint64_t>(pos.size(), pos_cap) * 4);
-    });
-    return rc ? rc : bad;
-}
-
-int sahara_interleave_rc(const uint8_t* reads, uint64_t n_reads, uint32_t len, uint32_t sigma, uint8_t* out) {
-    return guarded([&] {
-        if (sigma != 5 && sigma != 6) throw Error("sigma must be 5 or 6");
-        uint8_t comp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (sigma == 6) { comp[1] = 5; comp[2] = 3; comp[3] = 2; comp[4] = 4; comp[5] = 1; }
-        else            { comp[1] = 4; comp[2] = 3; comp[3] = 2; comp[4] = 1; }
-        for (uint64_t i = 0; i < n_reads; ++i) {
-            const uint8_t* r = reads + i * len;
-            uint8_t* f = out + (2 * i) * len;
-            uint8_t* b = out + (2 * i + 1) * len;
-            std::memcpy(f, r, len);
-            for (uint32_t j = 0; j < len; ++j) b[j] = comp[r[len - 1 - j] & 7];
-        }
-    });
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // ctx.h — the per-device context of libsahara_hip.so and what the C ABI
-// (capi.cpp), the query staging (staging.cpp) and the batch pipeline
+// (capi*.cpp), the query staging (staging.cpp) and the batch pipeline
 // (pass.cpp) share.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -17,6 +17,7 @@
 
 #include "../../include/sahara_hip.h"
 #include "device_index.h"
+#include "hit_route.h"
 #include "host_pool.h"
 #include "pass_plan.h"
 #include "search.h"
@@ -272,16 +273,18 @@ struct Ctx {
     struct Sink {
         bool staged = false;              // patterns are staged: sahara_gpu_run may search them
         bool streaming = false;           // ... chunk by chunk during the pass (Upload)
-        // host sink of sahara_gpu_search: each batch's sorted hits go to host
-        // memory on stF while later batches search: whole into pinned memory
-        // (pinned), or as 8-B records that the Expander expands (compact)
-        sahara_hit* sink = nullptr;
+        // where each batch's sorted hits go on stF while later batches search
+        // (hit_route.h: the entry point sets it, Pass::finish asks decideBatch)
+        HitRoute route = HitRoute::Device;
+        bool wholeFallback = false;       // CallRoute's (Expander into a pinned sink)
+        // the host sink: whole hits (PinnedWhole, Expander) or 8-B records
+        // (Records; null when that call's buffer is not page-locked)
+        void* host = nullptr;
+        sahara_hit* hits() const { return static_cast<sahara_hit*>(host); }
+        uint64_t* recs() const { return static_cast<uint64_t*>(host); }
         uint64_t cap = 0, done = 0;       // hits (records) the sink holds; those on their way into it
         bool ok = false;                  // every batch so far went into the sink
-        bool compact = false, pinned = false;
         uint64_t downJobs = 0;            // batches handed to the expander this call
-        uint64_t* blockRecs = nullptr;    // sahara_gpu_search_reads_compact's sink (below)
-        bool recs = false;                // ... its call: compact records are what it returns (sink pinned or not)
         // --max_hits n applied per batch on the device (single-part indexes;
         // limitBatch), 0: off
         uint32_t limitN = 0;
@@ -296,7 +299,7 @@ struct Ctx {
     std::unique_ptr<Expander> expander;
     // sahara_gpu_search_reads_compact: each batch's hits as 8-B records in
     // HBM (outRecs, at the batch's place among the call's hits) and copied by a
-    // copy engine on stF into the pinned host buffer sk.blockRecs (sk.cap records); per
+    // copy engine on stF into the pinned host buffer sk.recs() (sk.cap records); per
     // batch its first qid and one past its last record (the blocks of
     // sahara_hit_blocks). (Written by the kernel straight into the sink over
     // PCIe, the records held CU slots beside the text phase: C3 592M against
@@ -448,6 +451,7 @@ int guarded(F&& f) {
 bool hitLess(const sahara_hit& a, const sahara_hit& b);
 void limitHits(std::vector<sahara_hit>& v, uint32_t n);
 void handOver(const std::vector<sahara_hit>& v, sahara_hit** hits, uint64_t* n_hits);
+// capi_ctx.cpp: context lifecycle and placement
 Ctx* newCtx(int device);
 unsigned hostThreads(const Ctx* c, unsigned cap);
 Ctx* ctxOf(void* p);
@@ -492,6 +496,21 @@ void stageStreamed(Ctx* c, const uint8_t* src, uint64_t rows, bool rc, uint64_t 
                    int edit, const PackedReads* packed = nullptr);
 void stage(Ctx* c, const uint8_t* ranks, uint64_t npat, uint32_t m, const uint32_t* pi, const uint32_t* l,
            const uint32_t* u, const uint32_t* ns, uint32_t nrounds, int edit);
+
+// capi.cpp: host buffers handed to the caller, and what the alignment calls
+// (capi_align.cpp) share with the search calls
+// a host buffer on its way to the caller, freed by freeHits (allocHits, allocPinned) or std::free
+using HostBuf = std::unique_ptr<void, void (*)(void*)>;
+void* allocPinned(size_t bytes, bool* pinned, size_t* capBytes, bool mayPin, bool always = false);
+void freeHits(void* p);
+void copyOut(Ctx* c, void* dst, const void* src, size_t bytes);
+// The query list of a reads call: n_reads reads, interleaved with their
+// reverse complements (reverse) and cut to `limit` patterns (--limit_queries
+// cuts the interleaved list, search.cpp:125-127); rows: the reads it takes.
+struct ReadRows {
+    uint64_t npat, rows;
+};
+ReadRows readRows(int reverse, uint64_t n_reads, uint64_t limit);
 
 // pass.cpp: one pass over the staged patterns (every part of the index)
 DeviceIndex& partOf(Ctx* c, uint32_t p);

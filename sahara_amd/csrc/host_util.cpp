@@ -256,7 +256,7 @@ void synthReads(const uint8_t* ranks, const uint64_t* recLens, uint64_t nrec, ui
 }  // namespace sahara
 
 namespace sahara {
-extern thread_local std::string g_err;  // sahara_gpu_last_error (capi.cpp)
+extern thread_local std::string g_err;  // sahara_gpu_last_error (capi_ctx.cpp)
 }
 
 // ------------------------------------------------------------ FASTA ingest --

@@ -27,8 +27,8 @@ void run(Ctx* c, bool count) {
     if (c->more.empty()) return runOne(c, count);
     // (rounds mask a query by its rows in one part; "found" is decided across the parts: capi.cpp bestOnHost)
     if (c->rounds.size() > 1) throw Error("a pass of several rounds needs a single-part index");
-    const ScopeExit sinkBack([c, sink = c->sk.sink] { c->sk.sink = sink; });
-    c->sk.sink = nullptr;
+    const ScopeExit routeBack([c, route = c->sk.route] { c->sk.route = route; });
+    c->sk.route = HitRoute::Device;
     sahara_stats T{};
     uint64_t total = 0;
     const auto t0 = std::chrono::steady_clock::now();
@@ -173,7 +173,7 @@ static PassPlan makePlan(Ctx* c, bool count, bool redo) {
     // text 3 + FM 2 883-905M and FM 3 847-890M, alternating runs on one box:
     // 115-131 VGPRs per FM wave leave the SIMDs' registers to the text waves
     // and the locate chain.)
-    P.maxBatch = maxBatchOf(k.batch, c->sk.streaming, c->nsearch, c->sk.blockRecs != nullptr);
+    P.maxBatch = maxBatchOf(k.batch, c->sk.streaming, c->nsearch, c->sk.route == HitRoute::Records);
     const uint64_t batchesHere = (c->npat + P.maxBatch - 1) / P.maxBatch;
     if (!serial && batchesHere > 1 && c->verify) bpc = 1;
     if (k.fmBpc) bpc = (int)std::max<long>(1, std::min<long>(fullBpc, *k.fmBpc));
@@ -612,34 +612,39 @@ struct Pass {
         // them: the record is the sort key with the batch-local query in
         // front, so nothing is decoded and nothing of the batch goes into
         // c->out (Ctx::wholeHits expands it should a reader of c->out ask).
+        // Where the batch goes is decided here, once (hit_route.h).
+        auto decide = [&](uint64_t r) {
+            return decideBatch({c->sk.route, c->sk.wholeFallback, c->sk.ok, c->nout, r, nb, c->sk.cap, c->sk.limitN,
+                                c->more.empty(), Ctx::kDownSlot});
+        };
+        BatchPlan d = decide(rows);
         const uint64_t end = c->nout + rows;
-        const bool toExpander = !c->sk.blockRecs && c->sk.ok && end <= c->sk.cap && c->sk.compact &&
-                                rows * sizeof(uint64_t) <= Ctx::kDownSlot;
-        const bool direct = (c->sk.recs || toExpander) && c->sk.limitN == 0 && c->more.empty() && nb < (1ull << 28);
         auto growFor = [&](auto& buf) {  // a device-resident output of the call, kept as it grows
-            if (end <= buf.cap) return;
+            if (end <= buf.cap || rows == 0) return;  // (no rows: the sorts write nothing)
             SH_HIP(hipStreamSynchronize(c->stF));  // sink copies may still read the old buffer
             buf.growKeeping(std::max<size_t>(end + end / 2, 1024), std::min<size_t>(c->nout, buf.cap), sC);
         };
-        if (direct || c->sk.recs) growFor(c->outRecs);
-        if (direct) {
+        if (d.needRecs) growFor(c->outRecs);
+        if (d.direct) {
             sortCompact(c->k0.ptr, c->k1.ptr, rows, c->qoff.ptr, (uint32_t)nb, c->big.ptr, nbig, c->huge.ptr, nhuge,
                         c->outRecs.ptr + c->nout, c->tmp.ptr, c->tmp.cap, sC);
-            if (rows) c->outStale = true;
+            c->outStale = true;
         } else {
             growFor(c->out);
             sortDecode(c->k0.ptr, c->k1.ptr, rows, c->qoff.ptr, (uint32_t)nb, c->big.ptr, nbig, c->huge.ptr, nhuge, q0,
                        c->I.dRecStarts.ptr, (uint32_t)c->I.recStarts.size(), c->out.ptr + c->nout, c->tmp.ptr,
                        c->tmp.cap, sC);
         }
-        if (c->sk.limitN)  // --max_hits: this batch's queries keep their n best positions (search_n)
+        if (c->sk.limitN) {  // --max_hits: this batch's queries keep their n best positions (search_n)
             rows = limitBatch(c->out.ptr + c->nout, rows, c->qoff.ptr, (uint32_t)nb, c->sk.limitN, c->limitCnt,
                               c->limitOff, c->limitBuf, c->tmp, &rec.kept, sC);
+            d = decide(rows);  // the rows kept are what leaves (never direct: the sort above stands)
+        }
         SH_HIP(hipEventRecord(c->sortDone, sC));
         c->batchQ0.push_back(q0);
         c->batchEnd.push_back(c->nout + rows);
-        c->batchDirect.push_back(direct && rows ? 1 : 0);
-        sinkBatch(q0, nb, rows, direct);
+        c->batchDirect.push_back(d.direct ? 1 : 0);
+        sinkBatch(q0, rows, d);
         launchLocateFlagsOut(c->small.ptr + kLocFlags, &rec.locateFlags, sC);
         SH_HIP(hipEventRecord(c->flagsDown, sC));
         if (P.sleepy) SH_HIP(hipEventRecord(c->flagsDownSleep, sC));
@@ -648,38 +653,35 @@ struct Pass {
         return true;
     }
 
-    // sahara_gpu_search's host sink: the batch's hits (`rows` from c->nout on)
-    // go to host memory on stF while later batches search, while they fit
-    // the sink: as compact records into blockRecs, compact through the
-    // Expander, whole into a pinned sink, or not at all (the rest of the call's
-    // hits then go after the pass). direct: the sort has written the batch's
-    // compact records into c->outRecs (finish); else kCompactHits makes them
-    // from the whole hits in c->out.
-    void sinkBatch(uint64_t q0, uint64_t nb, uint64_t rows, bool direct) {
-        if (!c->sk.ok || c->nout + rows > c->sk.cap) {
-            c->sk.ok = false;
-            return;
-        }
-        const bool compact = c->sk.compact && rows * sizeof(uint64_t) <= Ctx::kDownSlot && nb < (1ull << 28);
-        if (rows && c->sk.blockRecs) {
+    // The call's host sink: the batch's hits (`rows` from c->nout on) go to
+    // host memory on stF while later batches search, by the one copy that
+    // decideBatch chose (hit_route.h); once a batch takes none, the rest of
+    // the call's hits go after the pass. d.compactFirst: kCompactHits makes
+    // the records from the whole hits in c->out; else the sort has written
+    // them into c->outRecs (finish).
+    void sinkBatch(uint64_t q0, uint64_t rows, const BatchPlan& d) {
+        switch (d.copy) {
+        case BatchCopy::None: break;
+        case BatchCopy::RecordsDma:
             // compact records in HBM on sC (by the sort, or from the whole
             // hits: full grid, ~20 us), then one D2H copy on stF: a copy engine
             // moves them, no workgroup waits on PCIe writes beside the text phase
-            if (!direct)
+            if (d.compactFirst)
                 launchCompactHits(c->out.ptr + c->nout, rows, q0, c->I.dRecStarts.ptr, c->outRecs.ptr + c->nout, sC,
                                   1u << 16);
             SH_HIP(hipEventRecord(c->recsMade, sC));
             SH_HIP(hipStreamWaitEvent(c->stF, c->recsMade, 0));
-            SH_HIP(hipMemcpyAsync(c->sk.blockRecs + c->nout, c->outRecs.ptr + c->nout, rows * sizeof(uint64_t),
+            SH_HIP(hipMemcpyAsync(c->sk.recs() + c->nout, c->outRecs.ptr + c->nout, rows * sizeof(uint64_t),
                                   hipMemcpyDeviceToHost, c->stF));
-        } else if (rows && compact) {  // 8-B records, expanded on the host (Expander)
+            break;
+        case BatchCopy::ExpanderSlot: {  // 8-B records, expanded on the host (Expander)
             const uint64_t j = c->sk.downJobs++;
             const size_t slot = (size_t)(j % Ctx::kDownSlots);
             if (j >= Ctx::kDownSlots) c->expander->waitFor(j + 1 - Ctx::kDownSlots);  // the slot is read
             while (c->downEv.size() < Ctx::kDownSlots) c->downEv.emplace_back(hipEventDisableTiming);
             uint64_t* stage = c->downRing.ptr + slot * (Ctx::kDownSlot / sizeof(uint64_t));
             uint64_t* dev = c->outRecs.ptr + c->nout;
-            if (!direct) {
+            if (d.compactFirst) {
                 c->outC.reserve(Ctx::kDownSlots * (Ctx::kDownSlot / sizeof(uint64_t)));
                 dev = c->outC.ptr + slot * (Ctx::kDownSlot / sizeof(uint64_t));
                 launchCompactHits(c->out.ptr + c->nout, rows, q0, c->I.dRecStarts.ptr, dev, sC);
@@ -688,15 +690,17 @@ struct Pass {
             SH_HIP(hipStreamWaitEvent(c->stF, c->recsMade, 0));
             SH_HIP(hipMemcpyAsync(stage, dev, rows * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stF));
             SH_HIP(hipEventRecord(c->downEv[slot], c->stF));
-            c->expander->submit({c->downEv[slot], stage, c->sk.sink + c->nout, rows, q0});
-        } else if (rows && c->sk.pinned) {
-            SH_HIP(hipStreamWaitEvent(c->stF, c->sortDone, 0));
-            SH_HIP(hipMemcpyAsync(c->sk.sink + c->nout, c->out.ptr + c->nout, rows * sizeof(sahara_hit),
-                                  hipMemcpyDeviceToHost, c->stF));
-        } else if (rows) {  // neither fits: the rest goes after the pass
-            c->sk.ok = false;
+            c->expander->submit({c->downEv[slot], stage, c->sk.hits() + c->nout, rows, q0});
+            break;
         }
-        if (c->sk.ok) c->sk.done = c->nout + rows;
+        case BatchCopy::WholeDma:
+            SH_HIP(hipStreamWaitEvent(c->stF, c->sortDone, 0));
+            SH_HIP(hipMemcpyAsync(c->sk.hits() + c->nout, c->out.ptr + c->nout, rows * sizeof(sahara_hit),
+                                  hipMemcpyDeviceToHost, c->stF));
+            break;
+        }
+        c->sk.ok = d.ok;
+        if (d.ok) c->sk.done = c->nout + rows;
     }
 
     void finishCheck(uint64_t b) {
@@ -802,7 +806,7 @@ void runPass(Ctx* c, bool count, bool redo, sahara_stats& S, bool& overflow) {
     }
     c->nout = 0;
     c->sk.done = 0;
-    c->sk.ok = c->sk.sink != nullptr || c->sk.blockRecs != nullptr;
+    c->sk.ok = sinkStarts(c->sk.route);
     c->batchQ0.clear();
     c->batchEnd.clear();
     c->batchDirect.clear();
