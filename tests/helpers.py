@@ -51,6 +51,23 @@ def mutate_reads(rng, recs, n, m, k, sigma=6):
     return out
 
 
+def substituted_reads(rng, recs, n, m, k, sigma=6):
+    """Reads of length m sampled from the records with 0..k substitutions
+    (read i: i % (k + 1), at distinct positions, each to another of A C G T)
+    and no indel: what a Hamming search can find."""
+    out = np.zeros((n, m), np.uint8)
+    alpha = acgt(sigma)
+    long_enough = [r for r in recs if len(r) >= m]
+    for i in range(n):
+        r = long_enough[rng.integers(len(long_enough))]
+        p = rng.integers(0, len(r) - m + 1)
+        s = r[p:p + m].copy()
+        for j in rng.choice(m, size=i % (k + 1), replace=False):
+            s[j] = rng.choice(alpha[alpha != s[j]])
+        out[i] = s
+    return out
+
+
 def hits_as_rows(h):
     """HIT_DTYPE array or (n,4) u64 array -> sorted (n,4) array (qid, seq_id, pos, e)."""
     if h.dtype.names:

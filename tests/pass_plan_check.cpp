@@ -51,7 +51,49 @@ int main() {
     CHECK(!b9.exactWindow && b9.winBlocks == (224 + 62) / 32);  // patBlocks > 8: block-aligned start
     const TextGeometry d = textGeometry(221, 2, 7, 3);
     CHECK(!d.exactWindow && d.winBlocks == 8 && d.winBlocks == (225 + 62) / 32);
+    // the read lengths at which the geometry changes (tests/test_text_variants.py
+    // runs the kernels at each): {m, k, patBlocks = ceil(m / 32)} ->
+    // exactWindow, winBlocks; textStack = 2k + 2 throughout
+    struct Edge { uint32_t m, k, pat; bool exact; uint32_t win; };
+    for (const Edge& e : {
+             Edge{96, 2, 3, true, 4},     // 100 symbols in 4 blocks, pattern 3 blocks
+             Edge{97, 2, 4, true, 4},     // pattern 4 blocks: the shape of m = 100
+             Edge{124, 2, 4, true, 4},    // m + 2k = 128: the 4 blocks filled to the last symbol
+             Edge{125, 2, 4, true, 5},    // 129: a fifth block
+             Edge{128, 0, 4, true, 4},    // window = pattern = 4 full blocks
+             Edge{126, 1, 4, true, 4},
+             Edge{220, 2, 7, true, 7},    // 224: 7 blocks copied from 8 loads
+             Edge{221, 2, 7, false, 8},   // 225: 8 exact blocks would need 9 loads
+             Edge{225, 0, 8, false, 8},   // (225 + 62) / 32
+             Edge{225, 1, 8, false, 9},   // 227: (227 + 62) / 32, the 9 / 8 shape's lower end (226)
+             Edge{250, 3, 8, false, 9},
+             Edge{251, 3, 8, false, 9},   // 257: its upper end
+             Edge{252, 3, 8, false, 10},  // 258: (258 + 62) / 32
+             Edge{256, 0, 8, false, 9},   // pattern 8 full blocks
+             Edge{257, 0, 9, false, 9},   // pattern 9 blocks
+             Edge{640, 2, 20, false, 22}, Edge{672, 2, 21, false, 23}, Edge{673, 2, 22, false, 23}}) {
+        CHECK((e.m + 31) / 32 == e.pat);
+        const TextGeometry g = textGeometry(e.m, e.k, e.pat, 3);
+        if (g.exactWindow != e.exact || g.winBlocks != e.win || g.textStack != 2 * e.k + 2) {
+            std::fprintf(stderr, "m %u k %u: exact %d blocks %u stack %u\n", e.m, e.k, (int)g.exactWindow, g.winBlocks,
+                         g.textStack);
+            ++failures;
+        }
+    }
+    CHECK(textGeometry(226 - 2, 1, 7, 3).winBlocks == 9 && textGeometry(226 - 2, 1, 7, 3).exactWindow == false);
+    // the largest text phase that fits the 160 KB of LDS: three searches, k = 2.
+    // table 2 * 3 * m words; lanes 256 * (3 * (window + pattern blocks) + 2 * 6) words
+    CHECK(textGeometry(640, 2, 20, 3).lds == 3840 * 4 + 256 * (3 * (22 + 20) + 12) * 4);
+    CHECK(textGeometry(640, 2, 20, 3).lds == 156672);
+    CHECK(textGeometry(672, 2, 21, 3).lds == 4032 * 4 + 256 * (3 * (23 + 21) + 12) * 4);
+    CHECK(textGeometry(672, 2, 21, 3).lds == 163584 && 163584 <= 160 * 1024 && 160 * 1024 - 163584 == 256);
+    CHECK(textGeometry(673, 2, 22, 3).lds == 4038 * 4 + 256 * (3 * (23 + 22) + 12) * 4);
+    CHECK(textGeometry(673, 2, 22, 3).lds == 166680 && 166680 > 160 * 1024);
+    CHECK(textGeometry(128, 0, 4, 3).tableWords == kTextTableMin && textGeometry(129, 0, 5, 3).tableWords == 774);
     // FM phase
+    CHECK(fmLdsBytes(5, 80, 0) == 400 * 4 && fmLdsBytes(5, 80, 8) == 400 * 4 + 8 * 4096);  // m = 80, five searches
+    CHECK(fmLdsBytes(5, 80, 1) == 400 * 4 + 4096);
+    CHECK(fmLdsBytes(7, 80, 0) == 560 * 4 && fmLdsBytes(7, 80, 8) == 560 * 4 + 8 * 4096);  // h2-k3, 0..3 errors: seven
     for (uint32_t sigma : {4u, 5u, 6u}) {
         CHECK(fmStackCap(0, sigma) == fmStackCap(1, sigma) && fmStackCap(1, sigma) == 2 * sigma);
         CHECK(fmStackCap(3, sigma) == 3 * (2 * sigma - 2) + 2);
