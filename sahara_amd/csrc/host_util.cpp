@@ -60,7 +60,12 @@ IdxParts parseIdx(const uint8_t* buf, size_t bytes) {
     uint64_t nrec = 0, nf = 0, nr = 0, ns = 0;
     const uint64_t* rl = r.vec<uint64_t>(nrec);
     P.recLens.assign(rl, rl + nrec);
-    P.rate = (uint32_t)r.get<uint64_t>();
+    // the rate bounds every LF walk (kDensify, kLocate): 0 would fail each locate, and a value
+    // past 32 bits would be cut to another rate
+    const uint64_t rate = r.get<uint64_t>();
+    if (rate == 0 || rate > UINT32_MAX)
+        throw Error("implausible SA sampling rate in the .idx file: " + std::to_string(rate));
+    P.rate = (uint32_t)rate;
     P.bwtF = r.vec<uint8_t>(nf);
     P.bwtR = r.vec<uint8_t>(nr);
     // the u64/u32 vectors follow the n-byte BWTs, so they are in general NOT
