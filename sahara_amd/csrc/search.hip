@@ -684,8 +684,8 @@ __global__ __launch_bounds__(256) void kSearchFM(SearchArgs a) {
 // equal offsets:
 //   window  (winBlocks blocks of 32 symbols)     W[(3j+b)*256 + t], plane b
 //   pattern (patBlocks blocks of 32 symbols)     P[(3j+b)*256 + t]
-//   stack   (stackCap entries)                   S[d*256 + t]: uint2, or one
-//           packed word (PK: m <= 127, window <= 256 symbols, e <= 7)
+//   stack   (stackCap entries)                   S[d*256 + t]: always a uint2
+//           node (x, y) as below: pos in 16 bits, e in 4 (e <= 15)
 //
 // A lane's state is one DFS node `cur` (x = window offsets xo | yo << 16 of
 // the text t matched so far, y = pos | e << 16 | lastL << 20 | lastR << 22).

@@ -26,6 +26,8 @@ void packSchemeTable(const uint32_t* pi, const uint32_t* l, const uint32_t* u, u
             const uint32_t L = l[(size_t)s * m + p], U = u[(size_t)s * m + p];
             if (L > U || U > kMaxErrors) throw Error("scheme bounds must satisfy l <= u <= 15");
             if (p > 0) {
+                // (a connected order of m steps inside [0, m) is a permutation: the kernels read pattern[pi])
+                if (P[p] >= m) throw Error("scheme pi out of range");
                 if (P[p] == hi + 1) hi = P[p];
                 else if (lo > 0 && P[p] == lo - 1) lo = P[p];
                 else throw Error("scheme pi is not a connected order (search.cpp:191 expand)");
