@@ -24,7 +24,7 @@ constexpr uint32_t kAlignBlock = 64;  // one wave: the table of K = 8 is 19.1 KB
 static_assert(sizeof(sahara_alignment) == 24, "sahara_alignment is 24 B");
 static_assert(kAlignMaxErr == SAHARA_ALIGN_MAX_ERR && kAlignNone == SAHARA_ALIGN_NONE, "align_core.h mirrors the ABI");
 
-// (as search.hip bufferOf: loads past the end return 0 without a memory request)
+// (as search_text.hip bufferOf: loads past the end return 0 without a memory request)
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t alignBufferOf(const void* base, uint32_t bytes) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, (int)bytes, 0x00020000);
 }

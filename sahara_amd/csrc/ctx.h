@@ -464,11 +464,10 @@ void uploadViaRing(Ctx* c, void* dst, const void* src, size_t bytes, hipStream_t
 // source buffer is no longer read): before a new call stages, after a failed one
 void drainPacking(Ctx* c);
 
-// staging.cpp: scheme tables, the query packers, the streamed upload
+// staging.cpp: the FM scheme table (the text phase's is text_step.h's
+// textTable), the query packers, the streamed upload
 void packSchemeTable(const uint32_t* pi, const uint32_t* l, const uint32_t* u, uint32_t ns, uint32_t m,
                      std::vector<uint32_t>& out, uint32_t& maxErr);
-void textTable(const uint32_t* pi, const uint32_t* l, const uint32_t* u, uint32_t ns, uint32_t m,
-               const std::vector<uint32_t>& packed, std::vector<uint32_t>& out);
 bool hostHasAvx2();
 bool hostHasAvx512();
 uint64_t pack2Best(const uint8_t* in, uint8_t* out, uint64_t count, uint32_t sigma, uint64_t base,

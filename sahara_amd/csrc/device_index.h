@@ -154,7 +154,7 @@ struct PinnedBuf {  // page-locked host memory that only ever grows (contents ar
 // Text (and patterns) for the text phase as 3-bit-plane blocks: block i holds
 // symbols [32i, 32i+32) as {plane0, plane1, plane2, 0}, bit j of plane b =
 // bit b of symbol 32i+j. One 16-B load per 32 symbols, and per-symbol masks of
-// 32 symbols come out of 3 word operations (search.hip, kSearchTextBatch).
+// 32 symbols come out of 3 word operations (search_text.hip, kSearchTextBatch).
 constexpr uint64_t kTextPadBlocks = 4096;  // zero blocks after the text (text-phase windows)
 inline uint64_t text3Blocks(uint64_t n) { return (n + 31) / 32 + kTextPadBlocks; }
 

@@ -188,7 +188,7 @@ static PassPlan makePlan(Ctx* c, bool count, bool redo) {
     const bool textFits = text3Blocks(c->I.n) * 16 <= 0xFFFFFF00ull &&
                           P.maxBatch * c->patBlocks * 16 <= 0xFFFFFF00ull;
     P.textShape = textShapeOf(P.tx.winBlocks, c->patBlocks, P.tx.exactWindow);
-    auto textAlone = [&] { return textBlocksPerCU(sigma, c->edit, count, P.textShape, P.tx.lds); };
+    auto textAlone = [&] { return textBlocksPerCU(c->edit, count, P.textShape, P.tx.lds); };
     int tbpc = c->verify && c->m <= 2047 && P.tx.lds <= 160 * 1024 && textFits ? textAlone() : 0;
     // overlapped with the FM phase, three text workgroups per CU beside its one
     // (four would fit: r2 v8 measured text 4 against 3 in alternating pairs,
@@ -502,7 +502,7 @@ struct Pass {
             TextBatchArgs t = textArgs(c, P, sl, b, r);
             if (split0) {
                 t.taskCount = sl.small.ptr + kSwSeedTasks;
-                launchTextBatch(t, c->I.sigma, c->edit, P.count, P.textBlocks, P.tx.lds, sB);
+                launchTextBatch(t, c->edit, P.count, P.textBlocks, P.tx.lds, sB);
                 SH_HIP(hipEventRecord(sl.textMid0, sB));
                 SH_HIP(hipStreamWaitEvent(sB, sl.fmDone, 0));
                 SH_HIP(hipEventRecord(sl.textMid1, sB));
@@ -511,7 +511,7 @@ struct Pass {
                 t.work = sl.queues.ptr + kQueueFmTasks;
                 ++S.text_launches;
             }
-            launchTextBatch(t, c->I.sigma, c->edit, P.count, P.textBlocks, P.tx.lds, sB);
+            launchTextBatch(t, c->edit, P.count, P.textBlocks, P.tx.lds, sB);
             ++S.text_launches;
         }
         SH_HIP(hipEventRecord(ev.textDone, sB));

@@ -150,7 +150,7 @@ struct TextBatchArgs {
     uint32_t pats3Bytes;
     uint32_t m;
     uint32_t nsearch;
-    const uint2* table;      // nsearch * m: {packScheme | run << 25, a | b << 12} (capi.cpp textTable)
+    const uint2* table;      // nsearch * m rows (text_step.h: TextRow, textTable)
     const uint4* tasks;
     const uint32_t* taskCount;  // tasks written by the seed / FM kernels (device-side: no host round trip)
     const uint32_t* taskBegin;  // first task of this launch (device-side; nullptr: 0)
@@ -193,11 +193,11 @@ struct LocateArgs {
 };
 
 int searchBlocksPerCU(uint32_t sigma, bool edit, size_t lds);
-int textBlocksPerCU(uint32_t sigma, bool edit, bool count, int shape, size_t lds);
+// the text phase of one batch (search_text.hip, kSearchTextBatch): the compiled
+// shape that a geometry runs as, that variant's occupancy, its launch
 int textShapeOf(uint32_t winBlocks, uint32_t patBlocks, bool exactWindow);
-// the text phase of one batch (kSearchTextBatch)
-void launchTextBatch(const TextBatchArgs& a, uint32_t sigma, bool edit, bool count, uint32_t blocks, size_t lds,
-                     hipStream_t st);
+int textBlocksPerCU(bool edit, bool count, int shape, size_t lds);
+void launchTextBatch(const TextBatchArgs& a, bool edit, bool count, uint32_t blocks, size_t lds, hipStream_t st);
 void launchSeeds(const SeedArgs& a, uint32_t sigma, uint32_t blocks, hipStream_t st);
 // Between two rounds of a batch (besthits, pass.cpp): what a round consumes in
 // the slot is reset: the seed count and the queue words are zero afterwards,

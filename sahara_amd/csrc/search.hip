@@ -16,14 +16,14 @@
 // interval holds at most `split` rows, the node is handed to phase 2 as one
 // *text task* per row instead of being ranked further.
 //
-// Phase 2, kSearchTextBatch: a text task is a node whose string t has a single
-// occurrence. Extending it by symbol c is non-empty iff c is the text's own
-// next symbol, so the rest of its subtree is the same DFS run against the
-// text. The lane copies the window of the 4-bit text that the subtree can
-// reach (full SA: one read) and the packed pattern into LDS and expands the
-// subtree there, without touching HBM. Nodes whose remaining positions admit
-// no further error are decided by one comparison of the remaining pattern
-// against the window.
+// Phase 2, kSearchTextBatch (search_text.hip): a text task is a node whose
+// string t has a single occurrence. Extending it by symbol c is non-empty iff
+// c is the text's own next symbol, so the rest of its subtree is the same DFS
+// run against the text. The lane copies the window of the text that the
+// subtree can reach (full SA: one read) and the pattern, both as 3-bit-plane
+// blocks, into LDS and expands the subtree there, without touching HBM
+// (text_step.h: the step). Nodes whose remaining positions admit no further
+// error are decided 32 symbols per comparison of the pattern against the window.
 //
 // Both DFSs push the match child first and the error children above it and
 // continue with one error child in registers, so a stack holds at most the
@@ -52,30 +52,10 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "search.h"
+#include "search_device.h"
 
 namespace sahara {
 namespace {
-
-// Pointers that come from memory (the slot table), from integers (Occ line
-// addresses) or that may point to LDS or global memory (a stack level) are
-// generic: accesses through them are flat instructions, which also count
-// against the LDS counter and make every LDS wait wait for them (and a flat
-// access of LDS is slower than a ds_ one). Where they address global memory,
-// say so. (The host pass of this file parses kernel bodies too, where class
-// types in an address space do not convert: there the cast is a plain one.)
-#if defined(__HIP_DEVICE_COMPILE__)
-#define GLOB(T, p) ((__attribute__((address_space(1))) T*)(p))
-#else
-#define GLOB(T, p) ((T*)(p))
-#endif
-// A 16-B record through a global pointer: uint4 is a class type whose copy
-// goes through a generic reference (a flat access again), a native vector is not
-typedef uint32_t U32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint4 loadGlobal4(const uint4* p) {
-    const U32x4 v = *GLOB(const U32x4, p);
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
 
 // Swap a dword with the neighbour lane of the pair (DPP quad_perm [1,0,3,2]).
 __device__ __forceinline__ uint32_t pairSwap(uint32_t v) {
@@ -132,73 +112,6 @@ __device__ __forceinline__ uint32_t pick5(const uint32_t v[5], uint32_t i) {
 }
 
 __device__ __forceinline__ uint32_t nib(uint32_t word, uint32_t i) { return (word >> ((i & 7u) * 4u)) & 0xFu; }
-
-constexpr uint32_t kSeedChunk = 64;   // seeds a wave takes per atomic
-// text tasks a wave takes per atomic (<= 64; 64 / 32 / 16 measured 1088 / 1021 /
-// 891M reads/s at C3, profiles/r05_task_chunk_ab.txt)
-constexpr uint32_t kTaskChunk = 64;
-static_assert(kTaskChunk >= 1 && kTaskChunk <= 64, "a chunk's records sit one per lane");
-constexpr uint32_t kHitChunk = 64;    // hit / task slots a wave reserves per atomic
-
-// Per-wave slot reservation for append-only outputs (hits, tasks): ballot +
-// prefix count inside the wave's current range; a fresh range of kHitChunk
-// slots costs one atomic. All lanes must call it (wave-uniform).
-struct SlotRange {
-    uint32_t next = 0, end = 0;
-    __device__ __forceinline__ bool take(bool want, uint32_t lane, uint64_t ltMask, uint32_t* counter,
-                                         uint32_t& slot) {
-        const uint64_t m = __ballot(want);
-        if (!m) return false;
-        const uint32_t cnt = (uint32_t)__popcll(m);
-        const uint32_t rank = (uint32_t)__popcll(m & ltMask);
-        const uint32_t avail = end - next;
-        uint32_t base = 0;
-        if (cnt > avail) {
-            if (lane == 0) base = atomicAdd(counter, kHitChunk);
-            base = __shfl(base, 0);
-        }
-        slot = rank < avail ? next + rank : base + (rank - avail);
-        if (cnt > avail) { next = base + (cnt - avail); end = base + kHitChunk; }
-        else next += cnt;
-        return true;
-    }
-    // unused tail of the last range: empty records (len 0) for the locate scan
-    __device__ __forceinline__ void close(uint32_t lane, uint4* buf, uint32_t cap) {
-        for (uint32_t i = next + lane; i < end; i += 64)
-            if (i < cap) buf[i] = make_uint4(0u, 0u, 0u, 0u);
-    }
-};
-
-// Work queue split into kStripes stripes with one counter each (128 B apart):
-// a wave starts on the stripe of its XCD (blockIdx % 8) and moves on when it
-// is drained. A single counter serialises at ~90 chunk grabs per microsecond
-// device-wide; eight of them keep a chunk grab off the critical path.
-constexpr uint32_t kStripes = 8;
-constexpr uint32_t kStripeStride = 32;  // u32 between counters
-static_assert(kStripes * kStripeStride == kQueueWords, "a striped queue is one region of Ctx::Slot::queues");
-struct StripedQueue {
-    uint32_t* ctr;
-    uint32_t n, stripe, tries = 0;
-    __device__ StripedQueue(uint32_t* c, uint32_t total) : ctr(c), n(total), stripe(blockIdx.x % kStripes) {}
-    // next chunk [b, e) of at most `chunk` items (wave-uniform); false when all stripes are drained
-    __device__ bool next(uint32_t lane, uint32_t chunk, uint32_t& b, uint32_t& e) {
-        while (tries < kStripes) {
-            const uint32_t s0 = (uint32_t)((uint64_t)n * stripe / kStripes);
-            const uint32_t s1 = (uint32_t)((uint64_t)n * (stripe + 1) / kStripes);
-            uint32_t off = 0;
-            if (lane == 0) off = s0 < s1 ? atomicAdd(ctr + stripe * kStripeStride, chunk) : 0xFFFFFFFFu;
-            off = __shfl(off, 0);
-            if (off != 0xFFFFFFFFu && off < s1 - s0) {
-                b = s0 + off;
-                e = min(b + chunk, s1);
-                return true;
-            }
-            stripe = (stripe + 1) % kStripes;
-            ++tries;
-        }
-        return false;
-    }
-};
 
 // Children of one DFS node under policy P0 (docs/semantics.md), with the
 // stack discipline described at the top. `occ[c]` says whether the child of
@@ -674,620 +587,6 @@ __global__ __launch_bounds__(256) void kSearchFM(SearchArgs a) {
         atomicAdd(a.counters + kCtExtLines, (unsigned long long)cLines);
         atomicAdd(a.counters + kCtTextTasks, (unsigned long long)cTasks);
         if (cIter) atomicAdd(a.counters + kCtFmIter, (unsigned long long)cIter);
-    }
-}
-
-// ========================================================= phase 2: text ====
-//
-// LDS: table[S*m] (uint2: packed scheme | run << 25, covered [a, b)) | per
-// lane, interleaved so that the lanes of a wave hit consecutive banks at
-// equal offsets:
-//   window  (winBlocks blocks of 32 symbols)     W[(3j+b)*256 + t], plane b
-//   pattern (patBlocks blocks of 32 symbols)     P[(3j+b)*256 + t]
-//   stack   (stackCap entries)                   S[d*256 + t]: always a uint2
-//           node (x, y) as below: pos in 16 bits, e in 4 (e <= 15)
-//
-// A lane's state is one DFS node `cur` (x = window offsets xo | yo << 16 of
-// the text t matched so far, y = pos | e << 16 | lastL << 20 | lastR << 22).
-// Every micro-step is straight-line code — one stack read, one table read,
-// 8-symbol reads of the window on both sides of the span and of the pattern at
-// pi[pos] and pi[pos+1], three stack writes — so the
-// lanes of a wave stay converged. A node with e == u[pos] has no error child
-// in the forced run of positions that follows it (table `run`), so it takes
-// up to 8 forced matches at once: the DFS visits the same chain of nodes,
-// one micro-step per 16 of them.
-
-
-
-// ---- runs of symbols as bit masks: bit j = chain symbol j. Symbols come as
-// 3 bit planes (device_index.h), so the per-symbol equality of 32 symbols is
-// three word xors; the chain logic uses the low 16 bits.
-constexpr uint32_t kRun = 32;              // symbols per micro-step run (a forced node's match budget)
-constexpr uint32_t kRunMask = 0xFFFFFFFFu;
-// chain positions per micro-step of a node whose error children are forced:
-// the forced-run check of an error child at chain node i reads symbols
-// i .. i + 7 of the 32 (kChain + 7 <= kRun)
-constexpr uint32_t kChain = 25;
-__device__ __forceinline__ uint32_t onesR(uint32_t n) {  // symbols [0, n), capped at kRun
-    return n >= kRun ? kRunMask : (1u << n) - 1u;
-}
-__device__ __forceinline__ uint32_t beyondR(uint32_t n) { return kRunMask & ~onesR(n); }  // symbols >= n
-// bit j set iff bits j .. j+6 are all set (7 consecutive matches from j)
-__device__ __forceinline__ uint32_t run7(uint32_t m) {
-    const uint32_t m2 = m & (m >> 1), m4 = m2 & (m2 >> 2);
-    return m4 & (m2 >> 4) & (m >> 6);
-}
-struct Planes { uint32_t b0, b1, b2; };
-__device__ __forceinline__ uint32_t eqm(const Planes& p, const Planes& t) {
-    return ~((p.b0 ^ t.b0) | (p.b1 ^ t.b1) | (p.b2 ^ t.b2));
-}
-__device__ __forceinline__ Planes shr1(const Planes& p) { return {p.b0 >> 1, p.b1 >> 1, p.b2 >> 1}; }
-__device__ __forceinline__ Planes shr2(const Planes& p) { return {p.b0 >> 2, p.b1 >> 2, p.b2 >> 2}; }
-// 32 symbols from offset o of a lane's interleaved plane array (block i, plane
-// b at word (3i + b) * 256). o may be negative (down to -32): reads may run
-// past either end of the array into the lane's neighbouring LDS regions; callers
-// mask.
-__device__ __forceinline__ uint32_t read32(const uint32_t* A, int o, uint32_t b) {
-    const int i = o >> 5;
-    return __builtin_amdgcn_alignbit(A[(3 * i + 3 + (int)b) * 256], A[(3 * i + (int)b) * 256], (uint32_t)o & 31u);
-}
-// 32 symbols in chain order: right (fwd) from o, or left ending at o - 1 and
-// reversed (back: bit j = symbol o - 1 - j). Symbols outside the array are
-// whatever the LDS holds there (the window's block -1 is the table region,
-// kTextTableMin words, the pattern's is the window): the window's are masked
-// by its `avail`, the pattern's lie beyond the pattern, which the chain logic
-// never uses (tests/text_model.py reads arbitrary symbols there).
-__device__ __forceinline__ Planes chain32(const uint32_t* A, uint32_t o, bool fwd) {
-    const int off = (int)o - (fwd ? 0 : 32);
-    Planes r;
-    uint32_t v[3];
-#pragma unroll
-    for (uint32_t b = 0; b < 3; ++b) {
-        const uint32_t w = read32(A, off, b);
-        v[b] = fwd ? w : __builtin_bitreverse32(w);
-    }
-    r.b0 = v[0]; r.b1 = v[1]; r.b2 = v[2];
-    return r;
-}
-
-// Raw buffer resource over [base, base + bytes) (gfx9 dword3): loads at an
-// offset past the end return 0 without a memory request, so guarded loads
-// need no branch (and no wait at a branch join).
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t bufferOf(const void* base, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, (int)bytes, 0x00020000);
-}
-constexpr uint32_t kBufOOB = 0xFFFFFFFFu;  // offset of a load that returns 0
-
-// Copy two block arrays (window, pattern) from global memory into this lane's
-// interleaved LDS slots (3 words per block): all loads of up to 8 blocks of
-// each array are issued before the first store, so a task start costs one
-// memory round trip for m <~ 190.
-__device__ __forceinline__ void copyBlocks(uint32_t* DA, __amdgpu_buffer_rsrc_t RA, uint32_t offA, uint32_t na,
-                                           uint32_t* DB, __amdgpu_buffer_rsrc_t RB, uint32_t offB, uint32_t nb) {
-    const uint32_t n = max(na, nb);
-    for (uint32_t c = 0; c < n; c += 8) {
-        decltype(__builtin_amdgcn_raw_buffer_load_b128(RA, 0u, 0, 0)) va[8], vb[8];
-#pragma unroll
-        for (uint32_t i = 0; i < 8; ++i) {
-            const uint32_t j = c + i;
-            va[i] = __builtin_amdgcn_raw_buffer_load_b128(RA, j < na ? offA + 16u * j : kBufOOB, 0, 0);
-            vb[i] = __builtin_amdgcn_raw_buffer_load_b128(RB, j < nb ? offB + 16u * j : kBufOOB, 0, 0);
-        }
-#pragma unroll
-        for (uint32_t i = 0; i < 8; ++i) {
-            const uint32_t j = c + i;
-            if (j < na) { uint32_t* D = DA + 3u * j * 256u; D[0] = va[i][0]; D[256] = va[i][1]; D[512] = va[i][2]; }
-            if (j < nb) { uint32_t* D = DB + 3u * j * 256u; D[0] = vb[i][0]; D[256] = vb[i][1]; D[512] = vb[i][2]; }
-        }
-    }
-}
-
-// Same, but the window starts at any symbol: na blocks come from na + 1
-// source blocks funnel-shifted by sh symbols (na + 1 <= 8, nb <= 8).
-__device__ __forceinline__ void copyBlocksShifted(uint32_t* DA, __amdgpu_buffer_rsrc_t RA, uint32_t offA, uint32_t sh,
-                                                  uint32_t na, uint32_t* DB, __amdgpu_buffer_rsrc_t RB, uint32_t offB,
-                                                  uint32_t nb) {
-    decltype(__builtin_amdgcn_raw_buffer_load_b128(RA, 0u, 0, 0)) va[8], vb[8];
-#pragma unroll
-    for (uint32_t j = 0; j < 8; ++j) {
-        va[j] = __builtin_amdgcn_raw_buffer_load_b128(RA, j <= na ? offA + 16u * j : kBufOOB, 0, 0);
-        vb[j] = __builtin_amdgcn_raw_buffer_load_b128(RB, j < nb ? offB + 16u * j : kBufOOB, 0, 0);
-    }
-#pragma unroll
-    for (uint32_t j = 0; j < 7; ++j)
-        if (j < na) {
-            uint32_t* D = DA + 3u * j * 256u;
-            D[0] = __builtin_amdgcn_alignbit(va[j + 1][0], va[j][0], sh);
-            D[256] = __builtin_amdgcn_alignbit(va[j + 1][1], va[j][1], sh);
-            D[512] = __builtin_amdgcn_alignbit(va[j + 1][2], va[j][2], sh);
-        }
-#pragma unroll
-    for (uint32_t j = 0; j < 8; ++j)
-        if (j < nb) { uint32_t* D = DB + 3u * j * 256u; D[0] = vb[j][0]; D[256] = vb[j][1]; D[512] = vb[j][2]; }
-}
-
-// SHAPE fixes the window and pattern block counts at compile time, so that
-// the task-start copy is straight-line code with no per-block conditions (the
-// generic form, SHAPE 0, keeps ~30 block masks in spilled SGPRs and reloads
-// them at every task start: 1882 against 1311 instructions, 101 against 85
-// VGPRs; C3 850-863M -> 886-893M reads/s).
-//   1: window 4 blocks at an exact start, pattern 4 blocks (C2, C3: m = 100)
-//   2: window 9 blocks block-aligned, pattern 8 blocks (C5: m = 250, k = 3)
-struct TextShape { uint32_t win, pat; bool exact; };
-__host__ __device__ constexpr TextShape textShape(int shape) {
-    return shape == 1 ? TextShape{4, 4, true} : shape == 2 ? TextShape{9, 8, false} : TextShape{0, 0, false};
-}
-
-
-// ---- kSearchTextBatch: the text phase of one batch per launch. Its tasks
-// [*taskBegin, *taskCount) of the slot's list come from a striped queue; a
-// lane takes a task (text position, or SA row read here), copies the window
-// and pattern to LDS and runs the subtree's DFS against the text; leaves are
-// hits (qid, text position, e | kPosKnown), each ranked in its query's
-// segment as it is written (kLocate places them). (Round 5's persistent
-// variant, one launch per pass, measured 2-3x slower and was removed in r6:
-// DESIGN.md §3.4.)
-template <int SIGMA, bool EDIT, bool COUNT, int SHAPE = 0>
-__global__ __launch_bounds__(256) void kSearchTextBatch(TextBatchArgs a) {
-    extern __shared__ uint32_t lds[];
-    uint2* SC = reinterpret_cast<uint2*>(lds);
-    uint32_t* slot = lds + a.tableWords;  // >= kTextTableMin: the window's block -1 stays in LDS
-    for (uint32_t i = threadIdx.x; i < a.nsearch * a.m; i += blockDim.x) SC[i] = a.table[i];
-    __syncthreads();
-
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t ltMask = (1ull << lane) - 1ull;
-    constexpr TextShape kShape = textShape(SHAPE);
-    const uint32_t winBlocks = SHAPE ? kShape.win : a.winBlocks, patBlocks = SHAPE ? kShape.pat : a.patBlocks;
-    const bool exactWindow = SHAPE ? kShape.exact : a.exactWindow != 0u;
-    uint32_t* W = slot + threadIdx.x;
-    uint32_t* P = slot + 3u * winBlocks * 256u + threadIdx.x;
-    uint2* S = reinterpret_cast<uint2*>(slot + 3u * (winBlocks + patBlocks) * 256u) + threadIdx.x;
-    auto stackGet = [&](uint32_t d) -> uint2 { return S[d * 256u]; };
-    auto stackPut = [&](uint32_t d, const uint2& v) { S[d * 256u] = v; };
-    const uint32_t winLen = winBlocks * 32u;
-    const __amdgpu_buffer_rsrc_t textBuf = bufferOf(a.text3, a.text3Bytes);
-    const __amdgpu_buffer_rsrc_t patBuf = bufferOf(a.pats3, a.pats3Bytes);
-    const uint32_t m = a.m;
-    // this launch's tasks: [tBase, taskCount) of the batch's list
-    const uint32_t tEnd = min(*a.taskCount, a.taskCap);
-    const uint32_t tBase = a.taskBegin ? min(*a.taskBegin, tEnd) : 0u;
-    const uint32_t ntasks = tEnd - tBase;
-    const uint4* tasks = a.tasks + tBase;
-
-    uint32_t sp = 0, pid = 0, wb = 0, sBase = 0;
-    bool have = false, exhausted = false, bad = false;
-    uint32_t qNext = 0, qEnd = 0, filled = 0;
-    bool qDone = false;
-    // task chunks: the current one's records (one per lane) and the next one's,
-    // prefetched a chunk ahead so a refill needs no dependent task read
-    uint4 curRec = make_uint4(0, 0, 0, 0), nextRec = curRec;
-    uint32_t nBase = 0, nEnd = 0, qBase = 0;
-    bool haveNext = false;
-    // The prefetched chunk's records still hold SA rows. Their text positions
-    // are read at the next refill, beside its window loads (one round trip for
-    // both), or at the latest when the chunk becomes current.
-    bool nextRaw = false;
-    auto resolveNext = [&]() {
-        if (nextRaw) {  // wave-uniform
-            if (nBase + lane < nEnd && !(nextRec.y & kTaskPos)) nextRec.x = a.sa[nextRec.x];
-            nextRaw = false;
-        }
-    };
-    StripedQueue queue(a.work, ntasks);
-    {
-        uint32_t b = 0, e = 0;
-        if (queue.next(lane, kTaskChunk, b, e)) {
-            nBase = b;
-            nEnd = e;
-            if (b + lane < e) nextRec = tasks[b + lane];
-            haveNext = true;
-            nextRaw = true;
-        } else {
-            qDone = true;
-        }
-    }
-    SlotRange hitSlots;
-    uint32_t rankSlot = ~0u, rankVal = 0;  // the lane's last hit whose rank is not stored yet
-    uint2 cur = make_uint2(0, 0);
-    uint64_t cNodes = 0, tIter = 0, tActive = 0, tRefill = 0, cCmp = 0, cSteps = 0;
-    uint64_t cyRefill = 0, cyStep = 0, cyEmit = 0, t0 = 0, cSteal = 0;
-    // (count mode, a.probe) the first launch's wave lives on the wall clock:
-    // the queue seen drained, iterations and busy lanes before / after it.
-    // Only in count mode: it costs the product kernel 14 VGPRs and 12 SGPR spills.
-    constexpr bool kProbe = COUNT;
-    __shared__ uint64_t wBorn[4], wDrain[4];
-    if (kProbe && a.probe && lane == 0) wBorn[threadIdx.x >> 6] = wall_clock64(), wDrain[threadIdx.x >> 6] = 0;
-    uint32_t pIterPre = 0, pIterPost = 0, pActPre = 0, pActPost = 0;
-    uint64_t pwPreA = 0, pwPreB = 0, pwPostA = 0, pwPostB = 0, pw0 = 0, pw1 = 0;
-
-    for (;;) {
-        if (kProbe && a.probe) pw0 = wall_clock64();
-        // Starting a task costs a global round trip (window + pattern) that
-        // stalls the whole wave, so idle lanes are refilled in batches: once
-        // refillAt lanes are idle (or nothing else is left).
-        if (COUNT) t0 = clock64();
-        const bool idle = !have && sp == 0 && !exhausted;
-        const uint64_t idleMask = __ballot(idle);
-        const bool busy = __any(have || sp > 0);
-        const bool refill = !busy || __popcll(idleMask) >= a.refillAt;
-        const bool need = refill && idle;
-        uint64_t pending = refill ? idleMask : 0ull;
-        if (pending) resolveNext();
-        while (pending) {  // wave-uniform
-            if (qNext >= qEnd) {
-                // switch to the prefetched chunk, prefetch the one after it
-                if (!haveNext) break;
-                resolveNext();
-                qBase = nBase;
-                qNext = nBase;
-                qEnd = nEnd;
-                curRec = nextRec;
-                haveNext = false;
-                if (!qDone) {
-                    uint32_t b = 0, e = 0;
-                    if (!queue.next(lane, kTaskChunk, b, e)) {
-                        qDone = true;
-                    } else {
-                        nBase = b;
-                        nEnd = e;
-                        if (b + lane < e) nextRec = tasks[b + lane];
-                        haveNext = true;
-                        nextRaw = true;
-                    }
-                }
-                if (qNext >= qEnd) continue;
-            }
-            const uint32_t take = min(qEnd - qNext, (uint32_t)__popcll(pending));
-            const uint32_t rank = (uint32_t)__popcll(pending & ltMask);
-            const bool mine = ((pending >> lane) & 1ull) && rank < take;
-            // the chunk's task records sit one per lane: fetch ours by shuffle
-            const uint32_t srcLane = (qNext - qBase + rank) & 63u;
-            const uint4 t = make_uint4(__shfl(curRec.x, srcLane), __shfl(curRec.y, srcLane),
-                                       __shfl(curRec.z, srcLane), __shfl(curRec.w, srcLane));
-            if (mine && t.y != 0u) {  // |t| = 0: an unused reserved slot (SlotRange::close)
-                // ---- start a task (x = its text position): copy the pattern
-                // and the text window its subtree can reach
-                const uint32_t x = t.x;
-                pid = t.z;
-                sBase = (t.w >> 24) * m;
-                const uint32_t meta = t.w & 0x00FFFFFFu;
-                const uint32_t pos = meta & 0xFFFFu, e = (meta >> 16) & 0xFu;
-                const uint32_t ca = SC[sBase + pos].y & 0xFFFu;
-                const uint32_t K = (SC[sBase + m - 1u].x >> 20) & 0xFu;
-                const uint32_t left = ca + (K > e ? K - e : 0u);  // text the left side can still consume
-                wb = x > left ? x - left : 0u;  // window start
-                if (exactWindow) {              // at wb: m + 2k symbols fit in winBlocks blocks
-                    copyBlocksShifted(W, textBuf, (wb >> 5) * 16u, wb & 31u, winBlocks, P, patBuf,
-                                      pid * patBlocks * 16u, patBlocks);
-                } else {                        // at the block start below wb (31 more symbols)
-                    wb &= ~31u;
-                    copyBlocks(W, textBuf, (wb >> 5) * 16u, winBlocks, P, patBuf, pid * patBlocks * 16u, patBlocks);
-                }
-                cur = make_uint2((x - wb) | ((x + (t.y & 0xFFFFu) - wb) << 16), meta);
-                have = true;
-            }
-            pending &= ~__ballot(mine);
-            qNext += take;
-        }
-        if (qDone && !haveNext && qNext >= qEnd && need && !have) exhausted = true;
-        // ---- work stealing inside the wave once the task queue is dry (wave-
-        // uniform: the queue state is the wave's). A launch ends on its longest
-        // subtrees, each on one lane while the others idle (C5: lanes busy
-        // 0.655 of the time); an idle lane takes the bottom (shallowest, so
-        // largest) stack entry of a busy lane, with that lane's window and
-        // pattern copied slot to slot in LDS, and the task state (pattern id,
-        // window start, scheme row) by shuffle. The DFS of the entry is the
-        // same whichever lane runs it, so the hits are too.
-        if (a.stealAt && qDone && !haveNext && qNext >= qEnd) {
-            const bool thief = !have && sp == 0u;
-            const uint64_t I = __ballot(thief);
-            const uint64_t D = __ballot(sp >= 2u || (sp == 1u && have));
-            const uint32_t nI = (uint32_t)__popcll(I), nD = (uint32_t)__popcll(D);
-            if (nI >= a.stealAt && nD) {  // wave-uniform
-                const uint32_t n = min(nI, nD);
-                const uint32_t r = (uint32_t)__popcll(I & ltMask);
-                // donor of thief rank r: the r-th set bit of D
-                uint32_t donor = 0, rr = r;
-                uint64_t dm = D;
-#pragma unroll
-                for (uint32_t w = 32; w; w >>= 1) {
-                    const uint32_t c = (uint32_t)__popcll(dm & ((1ull << w) - 1ull));
-                    if (rr >= c) { rr -= c; dm >>= w; donor += w; }
-                }
-                const bool takes = thief && r < n;
-                donor = takes ? donor : lane;
-                const uint32_t dPid = __shfl(pid, donor), dWb = __shfl(wb, donor), dBase = __shfl(sBase, donor);
-                const uint32_t dTid = (threadIdx.x & ~63u) | donor;
-                if (takes) {
-                    const uint32_t* src = slot + dTid;
-                    uint32_t* dst = slot + threadIdx.x;
-                    for (uint32_t k = 0; k < 3u * (winBlocks + patBlocks); ++k) dst[k * 256u] = src[k * 256u];
-                    const uint2 node = reinterpret_cast<const uint2*>(slot + 3u * (winBlocks + patBlocks) * 256u)[dTid];
-                    cur = node;
-                    pid = dPid;
-                    wb = dWb;
-                    sBase = dBase;
-                    have = true;
-                    if (COUNT) ++cSteal;
-                }
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                // donors (rank < n) drop their bottom entry
-                const bool gives = ((D >> lane) & 1ull) && (uint32_t)__popcll(D & ltMask) < n;
-                if (gives) {
-                    for (uint32_t d = 1; d < sp; ++d) stackPut(d - 1u, stackGet(d));
-                    --sp;
-                }
-            }
-        }
-        if (!__any(have || sp > 0 || (!exhausted && (!qDone || haveNext || qNext < qEnd)))) break;  // nothing left
-        if (kProbe && a.probe) {
-            if (qDone && lane == 0 && wDrain[threadIdx.x >> 6] == 0) wDrain[threadIdx.x >> 6] = wall_clock64();
-            const uint32_t act = (uint32_t)__popcll(__ballot(have || sp > 0));
-            if (qDone) { ++pIterPost; pActPost += act; } else { ++pIterPre; pActPre += act; }
-            pw1 = wall_clock64();
-        }
-        if (COUNT) {
-            const uint64_t act = __ballot(have || sp > 0);
-            if (lane == 0) { ++tIter; tActive += (uint64_t)__popcll(act); tRefill += refill ? 1u : 0u; }
-            const uint64_t t1 = clock64();
-            cyRefill += t1 - t0;
-            t0 = t1;
-        }
-
-        // ---- up to a.steps micro-steps per lane; a lane that reaches a leaf
-        // holds it (stalls) until the emission below
-        bool leaf = false;
-        uint32_t leafStart = 0, leafE = 0;
-        for (uint32_t step = 0; step < a.steps; ++step) {
-            const bool pop = !have && !leaf && sp > 0;
-            const uint2 top = stackGet(pop ? sp - 1u : 0u);
-            if (pop) { cur = top; --sp; have = true; }
-            const bool live = have && !leaf;
-            if (!__any(live)) break;  // wave-uniform
-
-            const uint32_t pos = cur.y & 0xFFFFu;
-            const uint32_t xo = cur.x & 0xFFFFu, yo = cur.x >> 16;
-            const uint32_t e = (cur.y >> 16) & 0xFu;
-            const uint32_t lastL = (cur.y >> 20) & 3u, lastR = (cur.y >> 22) & 3u;
-            const uint2 tab = SC[sBase + min(pos, m - 1u)];
-            const uint32_t t0 = tab.x;
-            const uint32_t q0 = t0 & 0xFFFFu, lb0 = (t0 >> 16) & 0xFu, ub0 = (t0 >> 20) & 0xFu;
-            const bool r0 = (t0 >> 24) & 1u;
-            const uint32_t run0 = t0 >> 25, same0 = (tab.y >> 24) & 0x7Fu;
-
-            // ---- pattern symbols from pi[pos] in this step's direction and
-            // the text symbols beyond the span on that side, both in chain
-            // order (symbol j of the chain in bit j); text past the window
-            // edge or before the text start reads as 0 and never matches.
-            // One read each at a side-dependent offset (a left run ends at the
-            // position and is bit-reversed), so the lanes of both sides share it
-            const Planes P16 = chain32(P, r0 ? q0 : q0 + 1u, r0);
-            const Planes T16 = chain32(W, r0 ? yo : xo, r0);
-            const uint32_t avail = r0 ? (winLen > yo ? winLen - yo : 0u) : xo;
-            const uint32_t VT = onesR(avail);
-            const uint32_t E0 = eqm(P16, T16) & VT;                 // p_j == t_j     (M chain, S runs)
-            const uint32_t ED = eqm(P16, shr1(T16)) & (VT >> 1);    // p_j == t_{j+1} (D runs)
-            const uint32_t EI = eqm(shr1(P16), T16) & VT;           // p_{j+1} == t_j (I runs)
-            const uint32_t TZ = (T16.b0 | T16.b1 | T16.b2) & VT;    // t_j is a symbol (not '$' / edge)
-
-            const bool atLeaf = live && pos == m;
-            const bool node = live && pos < m;
-            const bool forced = e == ub0;          // no error child here or in the rest of the run
-            const bool kidsF = e + 1u == ub0;      // the error children are forced nodes
-            const bool mOK = lb0 <= e && e <= ub0;
-            const bool misOK = lb0 <= e + 1u && e + 1u <= ub0;
-            const uint32_t side = r0 ? lastR : lastL;
-            // chain budget: a forced node matches up to kRun symbols; a node
-            // whose error children are forced walks up to kChain positions of
-            // its match chain (same direction, l and u), checking every error
-            // child's forced run on the way; any other node is expanded alone
-            const uint32_t B = forced ? min(run0, kRun)
-                                      : (kidsF ? max(1u, min(min(same0, run0 - 1u), kChain)) : 1u);
-            const uint32_t miss = ~E0 & kRunMask;
-            const uint32_t L = mOK ? min(B, miss ? (uint32_t)__builtin_ctz(miss) : kRun) : 0u;
-
-            // ---- error children of the chain nodes i < NN (node L = the mismatch)
-            const uint32_t NN = L < B ? L + 1u : B;
-            const uint32_t nodesM = node && !forced ? onesR(NN) : 0u;  // leaves / idle lanes: none
-            const uint32_t first = 1u;  // chain node 0 (= this node)
-            uint32_t Dm = EDIT ? (nodesM & TZ) : 0u;
-            if (pos == 0u || side == OP_I) Dm &= ~first;
-            uint32_t Im = EDIT && misOK ? nodesM : 0u;
-            if (side == OP_D) Im &= ~first;
-            // S at the first mismatch (not where M is merely disallowed: l > e)
-            bool Sx = node && !forced && L < B && misOK && ((TZ & ~E0) >> L) & 1u;
-            // forced runs: a child at e + 1 = u is forced for the rest of the run,
-            // and survives only if min(7, rest of the run) symbols match on its
-            // diagonal (positions past the run count as matches): R7x bit j =
-            // that check for a run starting at chain position j on diagonal x
-            const uint32_t bR = beyondR(run0), bR1 = beyondR(run0 - 1u);
-            const uint32_t R7E0 = run7(E0 | bR), R7ED = run7(ED | bR), R7EI = run7(EI | bR1);
-            if (kidsF) {
-                // D at i: p[i..] vs t[i+1..]; I at i: p[i+1..] vs t[i..]; S at L: p[L+1..] vs t[L+1..]
-                Dm &= R7ED;
-                Im &= R7EI;
-                Sx = Sx && ((R7E0 >> (L + 1u)) & 1u);
-            }
-            if (EDIT && node && e + 2u == ub0) {
-                // A node expanded alone whose error children are chain nodes:
-                // keep only the children whose subtree outlives their own first
-                // step. A child does if its match chain leaves the run or the
-                // 32 symbols read (chain length > kRun - 9), or one of its own
-                // error children (forced) passes the check above on its
-                // diagonal; no I right after D, no D right after I (policy P0).
-                // tests/text_model.py holds this to the plain DFS.
-                const uint32_t ED2 = eqm(P16, shr2(T16)) & (VT >> 2);   // p_j == t_{j+2}
-                const uint32_t EI2 = eqm(shr2(P16), T16) & VT;          // p_{j+2} == t_j
-                const uint32_t bR2 = run0 >= 2u ? beyondR(run0 - 2u) : kRunMask;
-                const uint32_t R7ED2 = run7(ED2 | bR), R7EI2 = run7(EI2 | bR2);
-                const uint32_t I2after = (R7E0 >> 1) & ~1u;  // bit j: I2 (back to diagonal 0) at chain node j > 0
-                constexpr uint32_t kLim = kRun - 9u;
-                if (Dm & first) {  // D child: p_j vs t_{j+1}
-                    const uint32_t LD = (uint32_t)__builtin_ctz(~ED);
-                    const bool keep = LD >= run0 || LD > kLim || ((R7ED >> (LD + 1u)) & 1u) ||
-                                      ((R7ED2 | I2after) & onesR(LD + 1u)) != 0u;
-                    if (!keep) Dm &= ~first;
-                }
-                if (Im & first) {  // I child: p_{x+1} vs t_x
-                    const uint32_t LI = ~EI ? (uint32_t)__builtin_ctz(~EI) : kRun;
-                    const bool keep = LI + 1u >= run0 || LI > kLim || ((R7EI >> (LI + 1u)) & 1u) ||
-                                      ((I2after | R7EI2) & onesR(LI + 1u)) != 0u;
-                    if (!keep) Im &= ~first;
-                }
-                if (Sx) {  // S child at the mismatch L = 0: p_x vs t_x, x >= 1
-                    const uint32_t rest = ~E0 & ~1u;
-                    const uint32_t LS = rest ? (uint32_t)__builtin_ctz(rest) : kRun;
-                    Sx = LS >= run0 || LS > kLim || ((R7E0 >> (LS + 1u)) & 1u) ||
-                         ((R7ED | R7EI) & ~1u & onesR(LS + 1u)) != 0u;
-                }
-            }
-            const bool contM = node && L >= B;  // the match chain continues at pos + B
-            uint32_t nSurv = (uint32_t)__popc(Dm) + (uint32_t)__popc(Im) + (Sx ? 1u : 0u);
-            // the lane continues with one child and stacks the others: a
-            // surviving error child first, the match chain below it
-            uint32_t Bc = B;
-            // Stack invariant (stackCap = 2k + 2): a node that stacks entries
-            // with e errors finds sp <= 2e + 2. One node expanded alone stacks
-            // <= 2; a chain may stack more only while the child it continues
-            // with (e + 1) still finds sp <= 2(e + 1) + 2.
-            if (nSurv && sp + nSurv + (contM ? 1u : 0u) - 1u > 2u * e + 4u) {
-                // not enough stack for this chain: expand its first node only
-                Bc = 1u;
-                Dm &= first;
-                Im &= first;
-                Sx = Sx && L == 0u;
-                nSurv = (uint32_t)__popc(Dm) + (uint32_t)__popc(Im) + (Sx ? 1u : 0u);
-            }
-            const bool contM1 = node && L >= Bc;
-            // cannot happen (the reserve rule above; tests/text_model.py): flagged, not handled
-            bad = bad || (node && nSurv && sp + nSurv + (contM1 ? 1u : 0u) - 1u > a.stackCap);
-
-            // ---- children as stack entries (x = span, y = meta). Per step:
-            // extending by n symbols adds n << 16 (right) or -n (left) to the
-            // span, one mad; a child's side memory is its operation on the
-            // extension side (MS once k forced matches follow it), the other
-            // side keeps its memory — except at pos 0, where the first
-            // operation sets both (for chain node i > 0 that was a match)
-            const int extMul = r0 ? 65536 : -1;
-            auto extend = [&](uint32_t span, uint32_t n) -> uint32_t { return span + (uint32_t)((int)n * extMul); };
-            const uint32_t shMine = r0 ? 22u : 20u, shOther = r0 ? 20u : 22u;
-            const uint32_t otherKept = pos ? (r0 ? lastL : lastR) : (uint32_t)OP_MS;
-            auto metaAt = [&](uint32_t i, uint32_t op, uint32_t k) -> uint32_t {
-                const uint32_t mine = k ? (uint32_t)OP_MS : op;
-                const uint32_t other = (pos == 0u && i == 0u) ? op : otherKept;
-                return (mine << shMine) | (other << shOther);
-            };
-            const uint32_t e1 = (e + 1u) << 16;
-            // forced matches after an error child whose run starts at chain node ii
-            const uint32_t kEnd = kidsF ? run0 : 0u;
-            const uint2 cM = make_uint2(extend(cur.x, Bc), (pos + Bc) | (e << 16) | metaAt(Bc, OP_MS, 0u));
-            if (nSurv) {  // the surviving error children; the last one stays in registers
-                uint32_t spw = sp;
-                uint2 pend = cM;
-                bool hasPend = contM1;
-                // one loop over all of them — D at chain node i (bit i), I at i
-                // (bit 32 + i), S at L (bit 63), in that order — so the wave
-                // runs max(nSurv) iterations rather than one loop per kind
-                uint64_t sv = (uint64_t)Dm | ((uint64_t)Im << 32) | (Sx ? 1ull << 63 : 0ull);
-                while (sv) {
-                    const uint32_t j = (uint32_t)__builtin_ctzll(sv);
-                    sv &= sv - 1ull;
-                    const bool isS = j == 63u, isD = j < 32u, isI = !isD && !isS;
-                    const uint32_t i = isS ? L : (j & 31u);
-                    const uint32_t ii = i + (isD ? 0u : 1u);  // chain node where its forced run starts
-                    const uint32_t k = ii < kEnd ? min(kEnd - ii, 7u) : 0u;
-                    const uint32_t op = isD ? (uint32_t)OP_D : (isI ? (uint32_t)OP_I : (uint32_t)OP_MS);
-                    const uint2 v = make_uint2(extend(cur.x, i + k + (isI ? 0u : 1u)), (pos + ii + k) | e1 | metaAt(i, op, k));
-                    if (hasPend) stackPut(min(spw++, a.stackCap - 1u), pend);
-                    pend = v;
-                    hasPend = true;
-                }
-                sp = min(spw, a.stackCap);
-                cur = pend;
-            } else if (node && contM1) {
-                cur = cM;
-            }
-
-            if (atLeaf) { leaf = true; leafStart = xo; leafE = e; }
-            have = live ? node && (nSurv || contM1) : have;
-            if (COUNT) {
-                cNodes += forced ? 0u : (node ? NN : 0u);
-                cCmp += (node && forced) ? 1u : 0u;
-                cSteps += node ? 1u : 0u;
-            }
-        }
-        if (COUNT) {
-            const uint64_t t1 = clock64();
-            cyStep += t1 - t0;
-            t0 = t1;
-        }
-        {
-            uint32_t s;
-            if (hitSlots.take(leaf, lane, ltMask, a.hitCount, s) && leaf) {
-                if (s < a.hitCap) {
-                    a.hits[s] = make_uint4(pid, wb + leafStart, 1u, leafE | kPosKnown);
-                    // the hit's row ranked in its query's segment (a.qcnt,
-                    // the FM phase's counts): the atomic's result is stored
-                    // at the lane's next emission, so that its round trip
-                    // overlaps the micro-steps in between (kLocate then
-                    // places the hit without an atomic of its own)
-                    if (rankSlot != ~0u) a.rank[rankSlot] = rankVal;
-                    rankVal = atomicAdd(a.qcnt + pid, 1u);
-                    rankSlot = s;
-                } else {
-                    atomicOr(a.flags, kFlagHits);
-                }
-                ++filled;
-            }
-        }
-        if (COUNT) cyEmit += clock64() - t0;
-        if (kProbe && a.probe) {
-            const uint64_t pw2 = wall_clock64();
-            if (qDone) { pwPostA += pw1 - pw0; pwPostB += pw2 - pw1; }
-            else { pwPreA += pw1 - pw0; pwPreB += pw2 - pw1; }
-        }
-    }
-    if (kProbe && a.probe && a.isFirst && lane == 0) {
-        const uint64_t wEnd = wall_clock64(), w0 = wBorn[threadIdx.x >> 6], wd = wDrain[threadIdx.x >> 6];
-        atomicMin(a.counters + kCtBornMin, (unsigned long long)w0);
-        atomicMax(a.counters + kCtBornMax, (unsigned long long)w0);
-        atomicMax(a.counters + kCtEndMax, (unsigned long long)wEnd);
-        atomicAdd(a.counters + kCtLifeSum, (unsigned long long)(wEnd - w0));
-        atomicMin(a.counters + kCtEndMin, (unsigned long long)wEnd);
-        if (wd) {
-            atomicMin(a.counters + kCtDryMin, (unsigned long long)wd);
-            atomicMax(a.counters + kCtDryMax, (unsigned long long)wd);
-            atomicAdd(a.counters + kCtDryRun, (unsigned long long)(wEnd - wd));
-            atomicAdd(a.counters + kCtDryWaves, 1ull);
-        }
-        atomicAdd(a.counters + kCtIterPre, (unsigned long long)pIterPre);
-        atomicAdd(a.counters + kCtActPre, (unsigned long long)pActPre);
-        atomicAdd(a.counters + kCtIterPost, (unsigned long long)pIterPost);
-        atomicAdd(a.counters + kCtActPost, (unsigned long long)pActPost);
-        atomicAdd(a.counters + kCtWallPreRefill, (unsigned long long)pwPreA);
-        atomicAdd(a.counters + kCtWallPreStep, (unsigned long long)pwPreB);
-        atomicAdd(a.counters + kCtWallPostRefill, (unsigned long long)pwPostA);
-        atomicAdd(a.counters + kCtWallPostStep, (unsigned long long)pwPostB);
-    }
-    hitSlots.close(lane, a.hits, a.hitCap);
-    if (rankSlot != ~0u) a.rank[rankSlot] = rankVal;
-    if (filled) atomicAdd(a.filled, filled);  // per-lane counts
-    if (__any(bad) && lane == 0) atomicOr(a.flags, kFlagTextStack);
-    if (COUNT) {
-        atomicAdd(a.counters + kCtTextNodes, (unsigned long long)cNodes);
-        if (lane == 0) {
-            atomicAdd(a.counters + kCtTextIter, (unsigned long long)tIter);
-            atomicAdd(a.counters + kCtTextActive, (unsigned long long)tActive);
-            atomicAdd(a.counters + kCtTextRefills, (unsigned long long)tRefill);
-            atomicAdd(a.counters + kCtCyRefill, (unsigned long long)cyRefill);
-            atomicAdd(a.counters + kCtCyStep, (unsigned long long)cyStep);
-            atomicAdd(a.counters + kCtCyEmit, (unsigned long long)cyEmit);
-        }
-        atomicAdd(a.counters + kCtCompareSteps, (unsigned long long)cCmp);
-        atomicAdd(a.counters + kCtTextSteps, (unsigned long long)cSteps);
-        if (cSteal) atomicAdd(a.counters + kCtStolen, (unsigned long long)cSteal);
     }
 }
 
@@ -1773,94 +1072,28 @@ struct SegOff {  // begin (d = 0) / end (d = 1) of a listed query's segment
     __host__ __device__ uint32_t operator()(const uint32_t& q) const { return (uint32_t)qoff[q + d]; }
 };
 
-template <int SIGMA>
-void launchFMT(const SearchArgs& a, bool edit, bool count, dim3 grid, size_t lds, hipStream_t st) {
-    if (edit) {
-        if (count) hipLaunchKernelGGL((kSearchFM<SIGMA, true, true>), grid, dim3(256), lds, st, a);
-        else       hipLaunchKernelGGL((kSearchFM<SIGMA, true, false>), grid, dim3(256), lds, st, a);
-    } else {
-        if (count) hipLaunchKernelGGL((kSearchFM<SIGMA, false, true>), grid, dim3(256), lds, st, a);
-        else       hipLaunchKernelGGL((kSearchFM<SIGMA, false, false>), grid, dim3(256), lds, st, a);
-    }
+// The compiled variants of kSearchFM, named once (sigma 5 or 6).
+const void* searchKernel(uint32_t sigma, bool edit, bool count) {
+#define SH_ROW(S, E) {(const void*)kSearchFM<S, E, false>, (const void*)kSearchFM<S, E, true>}
+    static const void* const kernels[2][2][2] = {{SH_ROW(5, false), SH_ROW(5, true)}, {SH_ROW(6, false), SH_ROW(6, true)}};
+#undef SH_ROW
+    return kernels[sigma == 5 ? 0 : 1][edit][count];
 }
-
-
 
 }  // namespace
 
-// the compile-time shape matching a launch (0: the generic kernel)
-int textShapeOf(uint32_t winBlocks, uint32_t patBlocks, bool exactWindow) {
-    for (int shape = 1; shape <= 2; ++shape) {
-        const TextShape t = textShape(shape);
-        if (winBlocks == t.win && patBlocks == t.pat && exactWindow == t.exact) return shape;
-    }
-    return 0;
-}
-
 int searchBlocksPerCU(uint32_t sigma, bool edit, size_t lds) {
     int b = 0;
-    const void* f;
-    if (sigma == 5) f = edit ? (const void*)kSearchFM<5, true, false> : (const void*)kSearchFM<5, false, false>;
-    else            f = edit ? (const void*)kSearchFM<6, true, false> : (const void*)kSearchFM<6, false, false>;
-    SH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, f, 256, lds));
+    SH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, searchKernel(sigma, edit, false), 256, lds));
     return b < 1 ? 1 : b;
-}
-
-template <int SIGMA>
-const void* textBatchKernelOf(bool edit, bool count, int shape) {
-#define SH_TB(S)                                                                                         \
-    if (shape == S)                                                                                      \
-        return edit ? (count ? (const void*)kSearchTextBatch<SIGMA, true, true, S>                       \
-                             : (const void*)kSearchTextBatch<SIGMA, true, false, S>)                     \
-                    : (count ? (const void*)kSearchTextBatch<SIGMA, false, true, S>                      \
-                             : (const void*)kSearchTextBatch<SIGMA, false, false, S>);
-    SH_TB(1)
-    SH_TB(2)
-    SH_TB(0)
-#undef SH_TB
-    return nullptr;
-}
-
-int textBlocksPerCU(uint32_t sigma, bool edit, bool count, int shape, size_t lds) {
-    // (the variant that is launched: its registers differ by shape and count mode)
-    int b = 0;
-    const void* f = sigma == 5 ? textBatchKernelOf<5>(edit, count, shape) : textBatchKernelOf<6>(edit, count, shape);
-    SH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, f, 256, lds));
-    return b;
 }
 
 void launchSearch(const SearchArgs& a, uint32_t sigma, bool edit, bool count, uint32_t blocks, size_t lds,
                   hipStream_t st) {
-    if (sigma == 5) launchFMT<5>(a, edit, count, dim3(blocks), lds, st);
-    else            launchFMT<6>(a, edit, count, dim3(blocks), lds, st);
-    SH_HIP(hipGetLastError());
+    void* args[] = {const_cast<SearchArgs*>(&a)};
+    SH_HIP(hipLaunchKernel(searchKernel(sigma, edit, count), dim3(blocks), dim3(256), args, lds, st));
 }
 
-template <int SIGMA, int SHAPE>
-void launchTextBatchShaped(const TextBatchArgs& a, bool edit, bool count, dim3 grid, size_t lds, hipStream_t st) {
-    if (edit) {
-        if (count) hipLaunchKernelGGL((kSearchTextBatch<SIGMA, true, true, SHAPE>), grid, dim3(256), lds, st, a);
-        else       hipLaunchKernelGGL((kSearchTextBatch<SIGMA, true, false, SHAPE>), grid, dim3(256), lds, st, a);
-    } else {
-        if (count) hipLaunchKernelGGL((kSearchTextBatch<SIGMA, false, true, SHAPE>), grid, dim3(256), lds, st, a);
-        else       hipLaunchKernelGGL((kSearchTextBatch<SIGMA, false, false, SHAPE>), grid, dim3(256), lds, st, a);
-    }
-}
-
-template <int SIGMA>
-void launchTextBatchT(const TextBatchArgs& a, bool edit, bool count, dim3 grid, size_t lds, hipStream_t st) {
-    const int shape = textShapeOf(a.winBlocks, a.patBlocks, a.exactWindow != 0u);
-    if (shape == 1) launchTextBatchShaped<SIGMA, 1>(a, edit, count, grid, lds, st);
-    else if (shape == 2) launchTextBatchShaped<SIGMA, 2>(a, edit, count, grid, lds, st);
-    else launchTextBatchShaped<SIGMA, 0>(a, edit, count, grid, lds, st);
-}
-
-void launchTextBatch(const TextBatchArgs& a, uint32_t sigma, bool edit, bool count, uint32_t blocks, size_t lds,
-                     hipStream_t st) {
-    if (sigma == 5) launchTextBatchT<5>(a, edit, count, dim3(blocks), lds, st);
-    else            launchTextBatchT<6>(a, edit, count, dim3(blocks), lds, st);
-    SH_HIP(hipGetLastError());
-}
 
 void launchSeeds(const SeedArgs& a, uint32_t sigma, uint32_t blocks, hipStream_t st) {
     if (sigma == 5) hipLaunchKernelGGL((kSeedItems<5>), dim3(blocks), dim3(256), 0, st, a);

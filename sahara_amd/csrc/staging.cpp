@@ -9,6 +9,7 @@
 #include <cstring>
 
 #include "ctx.h"
+#include "text_step.h"
 
 namespace sahara {
 
@@ -39,38 +40,6 @@ void packSchemeTable(const uint32_t* pi, const uint32_t* l, const uint32_t* u, u
             if (p > 0) right = P[p] > P[p - 1];
             else right = m > 1 ? (P[1] > P[0]) : 1u;
             out[(size_t)s * m + p] = packScheme(P[p], l[(size_t)s * m + p], u[(size_t)s * m + p], right);
-        }
-    }
-}
-
-// Text-phase table, two words per (search, pos):
-//   x = packScheme(...) | run << 25 — run = number of consecutive positions
-//       from pos (<= 127) on the same side with u == u[pos] and l <= u[pos]:
-//       a node at pos with e == u[pos] has no error child anywhere in that
-//       run, so the DFS is a forced chain of matches through it;
-//   y = a | b << 12 | same << 24 — pattern positions [a, b) covered before
-//       step pos; `same` (<= run) positions from pos share pos's l as well,
-//       so a chain of matches through them branches the same way at each.
-void textTable(const uint32_t* pi, const uint32_t* l, const uint32_t* u, uint32_t ns, uint32_t m,
-               const std::vector<uint32_t>& packed, std::vector<uint32_t>& out) {
-    out.assign((size_t)ns * m * 2, 0);
-    for (uint32_t s = 0; s < ns; ++s) {
-        const uint32_t* P = pi + (size_t)s * m;
-        const uint32_t* L = l + (size_t)s * m;
-        const uint32_t* U = u + (size_t)s * m;
-        const uint32_t* Q = packed.data() + (size_t)s * m;
-        uint32_t a = P[0], b = P[0];
-        for (uint32_t p = 0; p < m; ++p) {
-            const uint32_t right = (Q[p] >> 24) & 1u;
-            uint32_t run = 1, same = 1;
-            while (run < 127 && p + run < m && ((Q[p + run] >> 24) & 1u) == right && U[p + run] == U[p] &&
-                   L[p + run] <= U[p])
-                ++run;
-            while (same < run && L[p + same] == L[p]) ++same;
-            out[((size_t)s * m + p) * 2] = Q[p] | (run << 25);
-            out[((size_t)s * m + p) * 2 + 1] = a | (b << 12) | (same << 24);
-            a = std::min(a, P[p]);
-            b = std::max(b, P[p] + 1);
         }
     }
 }

@@ -688,7 +688,7 @@ def test_single_row_seeds_near_text_ends(gpu_device, m, k, gen):
 @pytest.mark.gpu
 @pytest.mark.parametrize("batch", ["61", "1000"])
 def test_text_phase_many_batches(gpu_device, monkeypatch, batch):
-    """The text phase per batch (search.hip kSearchTextBatch) with more
+    """The text phase per batch (search_text.hip kSearchTextBatch) with more
     batches than slots (61 patterns per batch: 14 batches over 5 slots),
     repeat-rich text with k = 3 (long tasks, work stealing): the oracle's hits
     through the device-resident pass (plain and count mode), the rank-form

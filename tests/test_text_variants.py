@@ -1,6 +1,6 @@
-"""Every compiled variant of the text kernel (kSearchTextBatch<SIGMA, EDIT,
-COUNT, SHAPE>: search.hip), the read lengths at which the text geometry
-changes (pass_plan.h textGeometry, search.hip textShapeOf), the edges of the
+"""Every compiled variant of the text kernel (kSearchTextBatch<EDIT, COUNT,
+SHAPE>: search_text.hip), the read lengths at which the text geometry
+changes (pass_plan.h textGeometry, search_text.hip textShapeOf), the edges of the
 seed stage (kSeedItems, seedCode, stageSchemes' kmerStart) and the scheduling
 knobs of pass_plan.h away from their defaults.
 

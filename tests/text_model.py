@@ -1,19 +1,23 @@
-"""Python model of kSearchTextBatch's chain micro-step (sahara_amd/csrc/search.hip).
+"""Python model of the text kernel's micro-step (sahara_amd/csrc/text_step.h,
+textStep; the kernel is search_text.hip's kSearchTextBatch).
 
 Test infrastructure: `chain()` restates, one node at a time and with Python
-sets instead of nibble masks, what a lane of the text kernel does per
+sets instead of 32-bit masks, what a lane of the text kernel does per
 micro-step — forced-run nodes matching up to RUN symbols, chain nodes walking
 up to CHAIN positions of a match chain and checking every error child's forced
 run, nodes two errors below their bound keeping only the error children that
 outlive their own first step, the stack reserve rule — and `plain()` is the
 textbook DFS of policy P0
 (docs/semantics.md) against the text. tests/test_text_model.py holds the two
-to the same leaf multiset from arbitrary DFS states.
+to the same leaf multiset from arbitrary DFS states; tests/test_text_step.py
+holds the real step (built for the host) to both, on the same cases
+(`chain_cases`, `true_read_cases`).
 """
 import collections
+import random
 
 MS, I_, D_ = 1, 2, 3
-RUN = 32    # symbols per micro-step run (kRun in search.hip)
+RUN = 32    # symbols per micro-step run (kRun in text_step.h)
 CHAIN = 25  # chain positions per micro-step of a node whose error children are forced (kChain)
 
 def sides(pos, right, lastL, lastR, op):
@@ -167,3 +171,99 @@ def chain(P, T, task, sch, edit, cap=100, RUN=RUN, CHAIN=CHAIN, PRUNE=True, stat
         if Sx:
             k = rl(L+1) if L+1 < run0 else 0; st.append(ext(L+1+k) + (pos+L+1+k, e+1) + metaAt(L, MS, k))
     return collections.Counter(out)
+
+
+def states(P, T, sch, edit, limit=300):
+    """DFS nodes from every start position (what the FM phase could hand over)."""
+    pi, l, u, dirs = sch
+    m = len(pi)
+    out = []
+    for start in range(len(T) + 1):
+        st = [(start, start, 0, 0, 0, 0)]
+        while st and len(out) < limit:
+            node = st.pop()
+            xs, ye, pos, e, lL, lR = node
+            if ye - xs >= 3:
+                out.append(node)
+            if pos == m:
+                continue
+            q, r = pi[pos], dirs[pos]
+            side = lR if r else lL
+            c = (T[ye] if ye < len(T) else 0) if r else (T[xs - 1] if xs > 0 else 0)
+            mOK, misOK = l[pos] <= e <= u[pos], l[pos] <= e + 1 <= u[pos]
+            delOK = edit and pos > 0 and e + 1 <= u[pos] and side != I_
+            insOK = edit and misOK and side != D_
+            a, b = (xs, ye + 1) if r else (xs - 1, ye)
+            if c != 0:
+                if c == P[q]:
+                    if mOK:
+                        st.append((a, b, pos + 1, e) + sides(pos, r, lL, lR, MS))
+                elif misOK:
+                    st.append((a, b, pos + 1, e + 1) + sides(pos, r, lL, lR, MS))
+                if delOK:
+                    st.append((a, b, pos, e + 1) + sides(pos, r, lL, lR, D_))
+            if insOK:
+                st.append((xs, ye, pos + 1, e + 1) + sides(pos, r, lL, lR, I_))
+    return out
+
+
+def chain_cases(seed):
+    """The cases of one seed: 60 random small schemes (one search each) over
+    small alphabets, a text that holds the pattern with a few edits, and up to
+    5 tasks each from arbitrary DFS states. Yields (P, T, sch, edit, cap, tasks)
+    with sch = (pi, l, u, dirs) and cap the stack bound 2k + 2."""
+    import oracle
+    rng = random.Random(seed)
+    for _ in range(60):
+        m, k = rng.randint(8, 36), rng.randint(1, 3)
+        gen = rng.choice(["h2-k2", "h2-k1", "pigeon", "backtracking", "h2-k3"])
+        ham = rng.random() < 0.3
+        pi, l, u = oracle.scheme(gen, 0, k, m, hamming=ham)
+        s = rng.randrange(len(pi))
+        pi, l, u = [int(v) for v in pi[s]], [int(v) for v in l[s]], [int(v) for v in u[s]]
+        dirs = [pi[p] > pi[p - 1] if p else (pi[1] > pi[0] if m > 1 else True) for p in range(m)]
+        sig = rng.choice([2, 3, 4])  # small alphabets: repeats, many surviving children
+        P = [rng.randint(1, sig) for _ in range(m)]
+        T = [rng.randint(1, sig) for _ in range(8)] + P[:] + [rng.randint(1, sig) for _ in range(8)]
+        for _ in range(rng.randint(0, 3)):
+            T[rng.randrange(8, 8 + m)] = rng.randint(1, sig)
+        for _ in range(rng.randint(0, 2)):
+            j = rng.randrange(8, 8 + m)
+            if rng.random() < 0.5:
+                del T[j]
+            else:
+                T.insert(j, rng.randint(1, sig))
+        if rng.random() < 0.2:
+            T[rng.randrange(len(T))] = 0  # a delimiter
+        edit = not ham
+        cap = 2 * max(max(u), 1) + 2
+        nodes = states(P, T, (pi, l, u, dirs), edit)
+        yield P, T, (pi, l, u, dirs), edit, cap, rng.sample(nodes, min(5, len(nodes)))
+
+
+def true_read_cases():
+    """h2-k2, m = 100, k = 2: 12 reads with two random edits against their
+    text, and every task the FM phase could hand over at depth 16. Yields
+    (P, T, sch, edit, cap, tasks) per read and search."""
+    import oracle
+    rng = random.Random(5)
+    m, k = 100, 2
+    pi, l, u = oracle.scheme("h2-k2", 0, k, m)
+    for _ in range(12):
+        T = [rng.randint(1, 4) for _ in range(400)]
+        P = T[150:250]
+        for _ in range(k):
+            j, r = rng.randrange(5, 95), rng.random()
+            if r < 0.33:
+                P[j] = rng.choice([c for c in (1, 2, 3, 4) if c != P[j]])
+            elif r < 0.66:
+                del P[j]
+                P.append(T[250])
+            else:
+                P.insert(j, rng.randint(1, 4))
+                P.pop()
+        for s in range(len(pi)):
+            sp, sl, su = [int(v) for v in pi[s]], [int(v) for v in l[s]], [int(v) for v in u[s]]
+            dirs = [sp[p] > sp[p - 1] if p else sp[1] > sp[0] for p in range(m)]
+            sch = (sp, sl, su, dirs)
+            yield P, T, sch, True, 2 * k + 2, [n for n in states(P, T, sch, True, limit=100000) if n[2] == 16]

@@ -6,8 +6,10 @@ every trip (how the r5 text kernel lost 4.5x: a returning atomic's register
 pending across the micro-step loop).
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude -Isahara_amd/csrc \\
-        --cuda-device-only -S sahara_amd/csrc/search.hip -o /tmp/search.s
-    python3 tools/asm_loops.py /tmp/search.s kSearchTextILi5ELb0ELb0ELi1E
+        --cuda-device-only -S sahara_amd/csrc/search_text.hip -o /tmp/search_text.s
+    python3 tools/asm_loops.py /tmp/search_text.s kSearchTextBatchILb1ELb0ELi1E
+
+(the text kernel's <EDIT, COUNT, SHAPE> variant; search.hip holds the others)
 
 A loop is a backward branch to a label of the same function; nested loops
 are listed separately (innermost first by size)."""
