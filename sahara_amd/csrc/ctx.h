@@ -27,7 +27,7 @@ namespace sahara {
 extern thread_local std::string g_err;  // sahara_gpu_last_error
 
 // Host side of sahara_gpu_search's compact hit download: batch by batch, the
-// 8-B records (search.hip kCompactHits) land in pinned staging memory on
+// 8-B records (hits.hip kCompactHits) land in pinned staging memory on
 // stream stF, and this thread expands them into the caller's sahara_hit
 // buffer (record id by binary search over the record starts) on a few worker
 // threads while later batches still search. Cuts the PCIe download to a third

@@ -11,6 +11,8 @@
 #include <optional>
 #include <vector>
 
+#include "fm_step.h"
+
 namespace sahara {
 
 // Text phase LDS: the scheme table comes first and takes at least one block of
@@ -144,11 +146,10 @@ inline std::vector<uint64_t> batchStarts(uint64_t npat, uint64_t maxBatch, std::
 }
 
 // FM phase: LDS bytes (the scheme table, then ldsDepth DFS levels of 16 B per
-// lane) and the entries a lane's DFS stack can hold
+// lane); the entries a lane's DFS stack can hold: fmStackCap (fm_step.h)
 inline size_t fmLdsBytes(uint32_t nsearch, uint32_t m, uint32_t ldsDepth) {
     return (size_t)((nsearch * m + 3u) & ~3u) * 4 + (size_t)ldsDepth * 256 * 16;
 }
-inline uint32_t fmStackCap(uint32_t maxErr, uint32_t sigma) { return std::max<uint32_t>(maxErr, 1) * (2 * sigma - 2) + 2; }
 
 // text phase geometry (LDS per lane: window | pattern | stack)
 // window: |t| + what both sides can still consume <= m + 2k symbols, plus

@@ -1,4 +1,5 @@
-// search.h — host-side launch interface of the search / locate kernels.
+// search.h — host-side launch interface of the search / locate kernels, grouped
+// by the unit that defines them.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -36,7 +37,7 @@ struct SearchArgs {
     uint32_t* filled;        // records actually written
     uint32_t* flags;         // Flag bits
     unsigned long long* counters;  // by Counter
-    uint4* tasks;            // text tasks (row, |t|, qid, meta | search << 24)
+    uint4* tasks;            // text tasks (fm_step.h: taskRecord)
     uint32_t taskCap;
     uint32_t* taskCount;
     uint32_t split;          // intervals of <= split rows go to the text phase (0: never)
@@ -97,7 +98,7 @@ enum Flag : uint32_t {
     kFlagTextStack = 16  // text DFS stack bound violated
 };
 // a slot's striped work queues (Ctx::Slot::queues), kQueueWords counter words
-// each (search.hip: kStripes * kStripeStride): the FM phase's seeds, the text
+// each (search_device.h: kStripes * kStripeStride): the FM phase's seeds, the text
 // phase's seed tasks, the tasks the FM phase appended
 constexpr uint32_t kQueueWords = 256;
 enum QueueAt : uint32_t { kQueueSeeds = 0, kQueueSeedTasks = kQueueWords, kQueueFmTasks = 2 * kQueueWords,
@@ -135,14 +136,10 @@ enum Counter : uint32_t {
     kCtStolen = 45,                                                      // text nodes stolen (all launches)
     kCtWallPreRefill = 46, kCtWallPreStep = 47, kCtWallPostRefill = 48, kCtWallPostStep = 49
 };
-// a task record whose x is already a text position (a k-mer seed with one
-// occurrence: DeviceIndex::kmerPos), not an SA row: bit 31 of its y (|t|)
-constexpr uint32_t kTaskPos = 0x80000000u;
-
 // One launch of the text phase over one batch's tasks [*taskBegin, *taskCount)
 // (kSearchTextBatch)
 struct TextBatchArgs {
-    const uint32_t* sa;      // full SA: task records carry SA rows (unless kTaskPos), the kernel reads their positions
+    const uint32_t* sa;      // full SA: task records carry SA rows (unless kTaskPos, fm_step.h), the kernel reads their positions
     const uint4* text3;      // text as 3-bit-plane blocks of 32 symbols (device_index.h)
     const uint4* pats3;      // the batch's patterns as 3-bit-plane blocks, patBlocks per pattern
     uint32_t patBlocks;
@@ -192,64 +189,29 @@ struct LocateArgs {
     uint32_t useSA;
 };
 
+// ---- search_fm.hip: the seeds and the FM phase of one batch (kSeedItems, kSearchFM)
 int searchBlocksPerCU(uint32_t sigma, bool edit, size_t lds);
-// the text phase of one batch (search_text.hip, kSearchTextBatch): the compiled
+void launchSeeds(const SeedArgs& a, uint32_t sigma, uint32_t blocks, hipStream_t st);
+void launchSearch(const SearchArgs& a, uint32_t sigma, bool edit, bool count, uint32_t blocks, size_t lds,
+                  hipStream_t st);
+
+// ---- search_text.hip: the text phase of one batch (kSearchTextBatch): the compiled
 // shape that a geometry runs as, that variant's occupancy, its launch
 int textShapeOf(uint32_t winBlocks, uint32_t patBlocks, bool exactWindow);
 int textBlocksPerCU(bool edit, bool count, int shape, size_t lds);
 void launchTextBatch(const TextBatchArgs& a, bool edit, bool count, uint32_t blocks, size_t lds, hipStream_t st);
-void launchSeeds(const SeedArgs& a, uint32_t sigma, uint32_t blocks, hipStream_t st);
-// Between two rounds of a batch (besthits, pass.cpp): what a round consumes in
-// the slot is reset: the seed count and the queue words are zero afterwards,
-// and kSwRoundTasks holds the task count so far, where the next round's text
-// launch begins. The hit count, filled, the flags, the task count (and qcnt,
-// rank) carry over.
-void launchRoundReset(uint32_t* small, uint32_t* queues, hipStream_t st);
-void launchPackPatterns(const uint8_t* src, uint64_t npat, uint32_t m, uint32_t patWords, uint32_t sigma,
-                        uint32_t* dst, uint32_t* bad, hipStream_t st);
-// n symbols, two per byte of nib (low nibble first) -> one per byte of dst
-void launchUnpackNibbles(const uint8_t* nib, uint8_t* dst, uint64_t n, hipStream_t st);
-void launchOffsetSeq(const sahara_hit* in, uint64_t n, uint64_t rec0, sahara_hit* out, hipStream_t st);
-// --max_hits on the device: one batch's hits limited in place, kept rows returned
-uint64_t limitBatch(sahara_hit* out, uint64_t rows, const uint64_t* qoff, uint32_t nq, uint32_t n,
-                    DevBuf<uint32_t>& kcnt, DevBuf<uint64_t>& koff, DevBuf<sahara_hit>& buf, DevBuf<char>& tmp,
-                    uint64_t* hostKept, hipStream_t st);
-// key / index buffers of the multi-part merge (kept by the context)
-struct MergeBufs {
-    DevBuf<uint64_t> k0, k1;
-    DevBuf<uint32_t> v0, v1;
-};
-void sortHitsByQid(const sahara_hit* in, uint64_t n, uint64_t nqid, sahara_hit* out, MergeBufs& B, DevBuf<char>& tmp,
-                   hipStream_t st);
-void launchCompactHits(const sahara_hit* h, uint64_t n, uint64_t qidBase, const uint64_t* starts, uint64_t* out,
-                       hipStream_t st, uint32_t maxBlocks = 8192);
-// a streamed chunk of 2-bit codes (read r0's first symbol at symbol `so` of
-// src, 0..3) straight into both pattern forms of the patterns [p0, p1)
-void launchPackFrom2(const uint8_t* src, uint32_t so, const uint32_t* exc, uint32_t nExc, uint64_t r0, uint64_t p0,
-                     uint64_t p1, uint32_t m, bool rc, uint32_t sigma, uint32_t patWords, uint32_t patBlocks,
-                     uint32_t* pats, uint4* pats3, hipStream_t st);
-// reads [r0, r1) (m bytes each) -> patterns [2 r0, min(2 r1, pEnd)): read, reverse complement, ...
-void launchInterleaveRC(const uint8_t* reads, uint64_t r0, uint64_t r1, uint32_t m, uint32_t sigma, uint64_t pEnd,
-                        uint8_t* pats, hipStream_t st);
-void launchSearch(const SearchArgs& a, uint32_t sigma, bool edit, bool count, uint32_t blocks, size_t lds,
-                  hipStream_t st);
-// locate + canonical order, per batch: querySegments (rows per query ->
-// segments; long segments listed in big, their count in *nbig, read back by
-// the host), launchLocate (keys into the segments), sortDecode (short
-// segments in registers, medium across a wave, long in LDS, huge by segmented
-// radix sort).
+
+// ---- locate_sort.hip: locate + canonical order, per batch: querySegments
+// (rows per query -> segments; long segments listed in big, their count in
+// *nbig, read back by the host), launchLocate (keys into the segments),
+// sortDecode (short segments in registers, medium across a wave, long in LDS,
+// huge by segmented radix sort).
 uint32_t scanTiles(uint32_t nq);  // u64 partials querySegments needs
 // qcnt: the batch's per-query row counts, which the search kernels add up
 // as they write the hits (SearchArgs::qcnt); all zero on return
 void querySegments(uint32_t* qcnt, uint32_t nq, uint64_t* qoff, uint64_t* partial, uint32_t* big, uint32_t* nbig,
                    uint32_t* huge, uint32_t* nhuge, hipStream_t st);
 void launchLocate(const LocateArgs& a, bool count, hipStream_t st);
-// a batch's totals into pinned host memory in one launch: the first 12 words
-// of its BatchRecord (the slot's counters, the row total, the long / huge
-// segment counts), and the slot reset: small, queues (the slot's counters and
-// queue words) and segCounts are zero afterwards
-void launchBatchTotals(uint32_t* small, uint32_t* queues, const uint64_t* rowTotal, uint32_t* segCounts, uint32_t* out,
-                       hipStream_t st);
 // the locate chain's flags word into pinned host memory (BatchRecord::locateFlags); zero afterwards
 void launchLocateFlagsOut(uint32_t* flags, uint32_t* out, hipStream_t st);
 size_t bigSortTempBytes(uint64_t rows, uint32_t nbig);
@@ -264,12 +226,54 @@ void sortDecode(uint64_t* k0, uint64_t* k1, uint64_t rows, const uint64_t* qoff,
 void sortCompact(uint64_t* k0, uint64_t* k1, uint64_t rows, const uint64_t* qoff, uint32_t nq, const uint32_t* big,
                  uint32_t nbig, const uint32_t* huge, uint32_t nhuge, uint64_t* out, void* tmp, size_t tmpBytes,
                  hipStream_t st);
+// a batch's totals into pinned host memory in one launch: the first 12 words
+// of its BatchRecord (the slot's counters, the row total, the long / huge
+// segment counts), and the slot reset: small, queues (the slot's counters and
+// queue words) and segCounts are zero afterwards
+void launchBatchTotals(uint32_t* small, uint32_t* queues, const uint64_t* rowTotal, uint32_t* segCounts, uint32_t* out,
+                       hipStream_t st);
+// Between two rounds of a batch (besthits, pass.cpp): what a round consumes in
+// the slot is reset: the seed count and the queue words are zero afterwards,
+// and kSwRoundTasks holds the task count so far, where the next round's text
+// launch begins. The hit count, filled, the flags, the task count (and qcnt,
+// rank) carry over.
+void launchRoundReset(uint32_t* small, uint32_t* queues, hipStream_t st);
+
+// ---- patterns.hip: query symbols into the search's two pattern forms
+void launchPackPatterns(const uint8_t* src, uint64_t npat, uint32_t m, uint32_t patWords, uint32_t sigma,
+                        uint32_t* dst, uint32_t* bad, hipStream_t st);
+void launchPackPatterns3(const uint8_t* src, uint64_t npat, uint32_t m, uint32_t patBlocks, uint4* dst,
+                         hipStream_t st);
+// n symbols, two per byte of nib (low nibble first) -> one per byte of dst
+void launchUnpackNibbles(const uint8_t* nib, uint8_t* dst, uint64_t n, hipStream_t st);
+// a streamed chunk of 2-bit codes (read r0's first symbol at symbol `so` of
+// src, 0..3) straight into both pattern forms of the patterns [p0, p1)
+void launchPackFrom2(const uint8_t* src, uint32_t so, const uint32_t* exc, uint32_t nExc, uint64_t r0, uint64_t p0,
+                     uint64_t p1, uint32_t m, bool rc, uint32_t sigma, uint32_t patWords, uint32_t patBlocks,
+                     uint32_t* pats, uint4* pats3, hipStream_t st);
+// reads [r0, r1) (m bytes each) -> patterns [2 r0, min(2 r1, pEnd)): read, reverse complement, ...
+void launchInterleaveRC(const uint8_t* reads, uint64_t r0, uint64_t r1, uint32_t m, uint32_t sigma, uint64_t pEnd,
+                        uint8_t* pats, hipStream_t st);
+
+// ---- hits.hip: a batch's hit records after the sort
+void launchDigest(const sahara_hit* h, uint64_t n, unsigned long long* out, hipStream_t st);
+void launchCopyHits(const sahara_hit* h, uint64_t n, uint64_t qidOffset, sahara_hit* dst, hipStream_t st);
+void launchOffsetSeq(const sahara_hit* in, uint64_t n, uint64_t rec0, sahara_hit* out, hipStream_t st);
+// --max_hits on the device: one batch's hits limited in place, kept rows returned
+uint64_t limitBatch(sahara_hit* out, uint64_t rows, const uint64_t* qoff, uint32_t nq, uint32_t n,
+                    DevBuf<uint32_t>& kcnt, DevBuf<uint64_t>& koff, DevBuf<sahara_hit>& buf, DevBuf<char>& tmp,
+                    uint64_t* hostKept, hipStream_t st);
+// key / index buffers of the multi-part merge (kept by the context)
+struct MergeBufs {
+    DevBuf<uint64_t> k0, k1;
+    DevBuf<uint32_t> v0, v1;
+};
+void sortHitsByQid(const sahara_hit* in, uint64_t n, uint64_t nqid, sahara_hit* out, MergeBufs& B, DevBuf<char>& tmp,
+                   hipStream_t st);
+void launchCompactHits(const sahara_hit* h, uint64_t n, uint64_t qidBase, const uint64_t* starts, uint64_t* out,
+                       hipStream_t st, uint32_t maxBlocks = 8192);
 // compact records of one batch (first qid qidBase) back into whole hits
 void launchExpandRecs(const uint64_t* recs, uint64_t n, uint64_t qidBase, const uint64_t* starts, uint32_t nrec,
                       sahara_hit* out, hipStream_t st);
-void launchPackPatterns3(const uint8_t* src, uint64_t npat, uint32_t m, uint32_t patBlocks, uint4* dst,
-                         hipStream_t st);
-void launchDigest(const sahara_hit* h, uint64_t n, unsigned long long* out, hipStream_t st);
-void launchCopyHits(const sahara_hit* h, uint64_t n, uint64_t qidOffset, sahara_hit* dst, hipStream_t st);
 
 }  // namespace sahara

@@ -1,6 +1,7 @@
-// search_device.h — device-side pieces that the kernels of search.hip and
-// search_text.hip share: global-memory accesses that say so, the per-wave
-// slot reservation of the append-only outputs and the striped work queue.
+// search_device.h — device-side pieces that the kernel units (search_fm.hip,
+// search_text.hip, locate_sort.hip, hits.hip) share: global-memory accesses
+// that say so, the per-wave slot reservation of the append-only outputs, the
+// striped work queue, the plan of an in-wave steal and the decode of a sorted key.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -95,6 +96,63 @@ struct StripedQueue {
         return false;
     }
 };
+
+// ---- work stealing inside a wave (wave-uniform call): of the idle lanes
+// (`thief`) and the lanes that can spare their bottom stack entry (`canGive`),
+// the first n = min(thieves, donors) of each pair up by rank, once stealAt
+// lanes are idle. A thief (takes) reads its donor's entry and state, all lanes
+// then fence (StealPlan::settle), and the donors (gives) drop the entry.
+struct StealPlan {
+    bool any, takes, gives;
+    uint32_t donor;  // the lane a thief takes from (its own lane when !takes: shuffles by donor stay defined)
+    // the thieves' reads complete before a donor's later writes reuse the entry
+    __device__ __forceinline__ void settle() const {
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+};
+__device__ __forceinline__ StealPlan stealPlan(bool thief, bool canGive, uint32_t stealAt, uint32_t lane,
+                                               uint64_t ltMask) {
+    const uint64_t I = __ballot(thief);
+    const uint64_t D = __ballot(canGive);
+    const uint32_t nI = (uint32_t)__popcll(I), nD = (uint32_t)__popcll(D);
+    if (nI < stealAt || !nD) return {false, false, false, lane};  // wave-uniform
+    const uint32_t n = min(nI, nD);
+    const uint32_t r = (uint32_t)__popcll(I & ltMask);
+    // donor of thief rank r: the r-th set bit of D
+    uint32_t donor = 0, rr = r;
+    uint64_t dm = D;
+#pragma unroll
+    for (uint32_t w = 32; w; w >>= 1) {
+        const uint32_t c = (uint32_t)__popcll(dm & ((1ull << w) - 1ull));
+        if (rr >= c) { rr -= c; dm >>= w; donor += w; }
+    }
+    const bool takes = thief && r < n;
+    const bool gives = ((D >> lane) & 1ull) && (uint32_t)__popcll(D & ltMask) < n;
+    return {true, takes, gives, takes ? donor : lane};
+}
+
+// ---- a sorted key (text position << 4 | e) of query qid -> the hit: the
+// record of the position by binary search over the record starts. `starts` is
+// whatever indexes to them — a global pointer or the LDS array itself, so that
+// LDS reads stay ds_ reads (a pointer that may be either is generic: see the
+// top). Texts of <= kLdsStarts records have their starts staged in LDS.
+constexpr uint32_t kLdsStarts = 256;
+template <typename Starts>
+__device__ __forceinline__ sahara_hit decodeKey(uint64_t k, uint64_t qid, const Starts& starts, uint32_t nrec) {
+    const uint64_t gpos = k >> 4;
+    uint32_t lo = 0, hi = nrec;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (starts[mid] <= gpos) lo = mid; else hi = mid;
+    }
+    sahara_hit h;
+    h.qid = qid;
+    h.seq_id = lo;
+    h.err = (uint32_t)(k & 15u);
+    h.pos = gpos - starts[lo];
+    return h;
+}
 
 }  // namespace
 }  // namespace sahara

@@ -1,4 +1,4 @@
-// search_text.hip — phase 2 of the search (search.hip has the overview): the
+// search_text.hip — phase 2 of the search (search_fm.hip has the overview): the
 // text tasks of one batch, each a DFS node whose string occurs once, expanded
 // against the text itself in LDS (gfx950).
 //
@@ -19,6 +19,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "fm_step.h"
 #include "search_device.h"
 #include "text_step.h"
 
@@ -213,15 +214,16 @@ struct TaskFeed {
     }
 };
 
-// ---- start a task (record t: x = its text position, y = |t|, z = pattern,
-// w = meta | search << 24): copy the pattern and the text window that its
-// subtree can reach into the lane's LDS
-__device__ __forceinline__ void startTask(TextLane& ln, const uint4& t, const LaneLds& L, uint32_t m,
+// ---- start a task (record rec, fm_step.h taskRecord, its x a text position
+// by now): copy the pattern and the text window that its subtree can reach
+// into the lane's LDS
+__device__ __forceinline__ void startTask(TextLane& ln, const uint4& rec, const LaneLds& L, uint32_t m,
                                           __amdgpu_buffer_rsrc_t textBuf, __amdgpu_buffer_rsrc_t patBuf) {
+    const TextTask t = taskOf({rec.x, rec.y, rec.z, rec.w});
     const uint32_t x = t.x;
-    ln.pid = t.z;
-    ln.sBase = (t.w >> 24) * m;
-    const uint32_t meta = t.w & 0x00FFFFFFu;
+    ln.pid = t.pid;
+    ln.sBase = t.search * m;
+    const uint32_t meta = t.meta;
     const uint32_t pos = meta & 0xFFFFu, e = (meta >> 16) & 0xFu;
     const uint32_t ca = L.row(ln.sBase + pos).coverBegin();
     const uint32_t K = L.row(ln.sBase + m - 1u).ub();
@@ -235,7 +237,7 @@ __device__ __forceinline__ void startTask(TextLane& ln, const uint4& t, const La
         copyBlocks(L.W, textBuf, (wb >> 5) * 16u, L.winBlocks, L.P, patBuf, ln.pid * L.patBlocks * 16u, L.patBlocks);
     }
     ln.wb = wb;
-    ln.cur = textNode(x - wb, x + (t.y & 0xFFFFu) - wb, meta);
+    ln.cur = textNode(x - wb, x + t.tlen - wb, meta);
     ln.have = true;
 }
 
@@ -249,26 +251,11 @@ __device__ __forceinline__ void startTask(TextLane& ln, const uint4& t, const La
 // a node.
 __device__ __forceinline__ bool stealStage(TextLane& ln, const LaneLds& L, uint32_t stealAt, uint32_t lane,
                                            uint64_t ltMask) {
-    const bool thief = !ln.have && ln.sp == 0u;
-    const uint64_t I = __ballot(thief);
-    const uint64_t D = __ballot(ln.sp >= 2u || (ln.sp == 1u && ln.have));
-    const uint32_t nI = (uint32_t)__popcll(I), nD = (uint32_t)__popcll(D);
-    if (nI < stealAt || !nD) return false;  // wave-uniform
-    const uint32_t n = min(nI, nD);
-    const uint32_t r = (uint32_t)__popcll(I & ltMask);
-    // donor of thief rank r: the r-th set bit of D
-    uint32_t donor = 0, rr = r;
-    uint64_t dm = D;
-#pragma unroll
-    for (uint32_t w = 32; w; w >>= 1) {
-        const uint32_t c = (uint32_t)__popcll(dm & ((1ull << w) - 1ull));
-        if (rr >= c) { rr -= c; dm >>= w; donor += w; }
-    }
-    const bool takes = thief && r < n;
-    donor = takes ? donor : lane;
-    const uint32_t dPid = __shfl(ln.pid, donor), dWb = __shfl(ln.wb, donor), dBase = __shfl(ln.sBase, donor);
-    const uint32_t dTid = (threadIdx.x & ~63u) | donor;
-    if (takes) {
+    const StealPlan p = stealPlan(!ln.have && ln.sp == 0u, ln.sp >= 2u || (ln.sp == 1u && ln.have), stealAt, lane, ltMask);
+    if (!p.any) return false;  // wave-uniform
+    const uint32_t dPid = __shfl(ln.pid, p.donor), dWb = __shfl(ln.wb, p.donor), dBase = __shfl(ln.sBase, p.donor);
+    const uint32_t dTid = (threadIdx.x & ~63u) | p.donor;
+    if (p.takes) {
         const uint32_t* src = L.slot + dTid;
         uint32_t* dst = L.slot + threadIdx.x;
         for (uint32_t k = 0; k < L.copyWords(); ++k) dst[k * 256u] = src[k * 256u];
@@ -279,15 +266,12 @@ __device__ __forceinline__ bool stealStage(TextLane& ln, const LaneLds& L, uint3
         ln.sBase = dBase;
         ln.have = true;
     }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    // donors (rank < n) drop their bottom entry
-    const bool gives = ((D >> lane) & 1ull) && (uint32_t)__popcll(D & ltMask) < n;
-    if (gives) {
+    p.settle();
+    if (p.gives) {  // donors drop their bottom entry
         for (uint32_t d = 1; d < ln.sp; ++d) L.stackPut(d - 1u, L.stackGet(d));
         --ln.sp;
     }
-    return takes;
+    return p.takes;
 }
 
 // ---- hit emission: leaves are hits (qid, text position, 1, e | kPosKnown)

@@ -15,7 +15,7 @@ rows of a million queries without an oracle run, already in canonical
 The query layouts of test_hit_chain_edges.py are data here (lists of counts;
 0 = a random pattern), so that the properties they exist for are asserted
 without a GPU. A "range" is 256 consecutive queries from the start of a batch:
-one workgroup of the sort (search.hip kSortDecode).
+one workgroup of the sort (locate_sort.hip kSortDecode).
 """
 import functools
 
@@ -31,7 +31,7 @@ SUBS = {3: 5, 8: 1, 9: 3, 64: 5, 2048: 7}
 LIMIT_PAIRS = ((3, 5), (8, 1), (64, 5), (2048, 7))
 N_RANDOM = 16  # patterns for count 0
 
-# the sort's tiers (search.hip): rows <= SMALL in a lane, <= MEDIUM in a wave,
+# the sort's tiers (locate_sort.hip): rows <= SMALL in a lane, <= MEDIUM in a wave,
 # <= LDS in a workgroup's LDS, more by the segmented radix sort; a range of
 # <= TILE rows is staged in LDS; the scan works on tiles of SCAN_TILE counts
 SMALL, MEDIUM, LDS, TILE, RANGE, SCAN_TILE = 8, 64, 2048, 1024, 256, 4096

@@ -178,7 +178,7 @@ def _mix64(x):
 
 def test_hits_digest_restates_kdigest():
     """bench.hits_digest (numpy, wrapping u64) against the kDigest formula in
-    plain Python integers (search.hip kDigest), order-independent."""
+    plain Python integers (hits.hip kDigest), order-independent."""
     rng = np.random.default_rng(5)
     h = np.zeros(3000, sa.HIT_DTYPE)
     h["qid"] = rng.integers(0, 1 << 40, len(h), dtype=np.uint64)

@@ -1,5 +1,5 @@
 """Streamed calls whose sink takes compact records sort each batch straight
-into them (search.hip kSortDecode<true>, kSortBigLds<true>, kDecodeBig<true>;
+into them (locate_sort.hip kSortDecode<true>, kSortBigLds<true>, kDecodeBig<true>;
 pass.cpp finish): no whole hit of such a batch is written on the device until
 a reader of the whole hits asks (Ctx::wholeHits: fetch, digest). Every sort
 tier over several batches, a sink that is too small and refilled from the

@@ -297,7 +297,7 @@ def _repeat_case():
 
 
 def test_sort_decode_tile_holds_every_tier(gpu_device):
-    """kSortDecode (search.hip) stages the rows of 256 consecutive queries in
+    """kSortDecode (locate_sort.hip) stages the rows of 256 consecutive queries in
     LDS when they fit its 1024-key tile. Here one such range mixes queries
     without hits with register-sorted (<= 8 rows), wave-sorted (9-64) and
     radix-sorted (> 64) segments, in shuffled order; the range before it holds
@@ -554,7 +554,7 @@ def test_fm_phase_work_stealing(gpu_device, monkeypatch, steal):
 @pytest.mark.gpu
 @pytest.mark.parametrize("n,batch", [(1, "257"), (2, "257"), (5, "257"), (3, "7")])
 def test_max_hits_on_the_device(gpu_device, monkeypatch, n, batch):
-    """--max_hits n limited per batch on the device (search.hip limitBatch)
+    """--max_hits n limited per batch on the device (hits.hip limitBatch)
     equals the documented policy (include/sahara_hip.h, test_golden's
     limit_rows) over the oracle's hits: repeat-rich text (queries with many
     positions and several error counts), several batches, reads and

@@ -1,4 +1,4 @@
-"""The chain between the search kernels and the caller's buffer (search.hip
+"""The chain between the search kernels and the caller's buffer (locate_sort.hip, hits.hip
 kTileSums .. kCompactHits), held at exact tier edges and past each grid cap.
 
 The text is tests/planted.py's: the rows of every query are known by

@@ -1,4 +1,4 @@
-"""The index kernels (index_build.hip) and kLocate's LF walk (search.hip) at
+"""The index kernels (index_build.hip) and kLocate's LF walk (locate_sort.hip) at
 other sampling rates and at the sizes where they change path.
 
 The case table is tests/index_cases.py's; what every case must give is the

@@ -72,7 +72,7 @@ def test_edit_inputs(name):
     assert 5 <= k <= 8 and c["reads"].shape == (n, m)
     per_q = np.bincount(c["want"][:, 0].astype(np.int64), minlength=n)
     print(f"  rows per query: max {per_q.max()}, queries with rows {np.count_nonzero(per_q)} of {n}")
-    assert per_q.max() > 2048  # the sort's "huge" tier (search.hip), with e up to k in it
+    assert per_q.max() > 2048  # the sort's "huge" tier (locate_sort.hip), with e up to k in it
     assert np.array_equal(c["scheme"][0], sa.search_scheme(gen, 0, k, m)[0])
 
 

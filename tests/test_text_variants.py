@@ -281,7 +281,7 @@ def _kmer_counts(recs, K, sigma):
 
 
 def _seed_expectation(recs, pats, scheme, K, sigma):
-    """The seed stage's rules (search.hip kSeedItems) over this input: (items
+    """The seed stage's rules (search_fm.hip kSeedItems) over this input: (items
     it keeps, items that become text tasks). A search whose first K steps admit
     no error starts from the K-mer at the least of their pattern positions: an
     item whose K-mer is absent from the text is dropped, one whose K-mer has a

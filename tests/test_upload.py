@@ -1,5 +1,5 @@
 """Streamed query upload at two bits per symbol (capi.cpp uploadChunk,
-pack2Avx2 / pack2Scalar; search.hip kUnpack2 / kPatchRank).
+pack2Avx2 / pack2Scalar; patterns.hip kUnpack2 / kPatchRank).
 
 CPU: the host packer against a numpy restatement of the format (symbol i at
 bits 2 (i % 4) of byte i / 4, A C G T = 0 1 2 3, dna5's N listed by position),

@@ -9,7 +9,7 @@ pending across the micro-step loop).
         --cuda-device-only -S sahara_amd/csrc/search_text.hip -o /tmp/search_text.s
     python3 tools/asm_loops.py /tmp/search_text.s kSearchTextBatchILb1ELb0ELi1E
 
-(the text kernel's <EDIT, COUNT, SHAPE> variant; search.hip holds the others)
+(the text kernel's <EDIT, COUNT, SHAPE> variant; search_fm.hip, locate_sort.hip, patterns.hip and hits.hip hold the others)
 
 A loop is a backward branch to a label of the same function; nested loops
 are listed separately (innermost first by size)."""
