@@ -303,6 +303,29 @@ int  sahara_gpu_align_stats(void* ctx, sahara_align_stats* stats);
 /* host only, no context: the extended CIGAR ("57=1X42=") of one record; returns its length, -1 if cap is too small or the record is NONE */
 int  sahara_cigar(const sahara_alignment* a, uint32_t len, char* buf, size_t cap);
 
+/* --- loci (docs/semantics.md "Loci") ---
+ * All-mode search reports every (qid, seq_id, pos, e) the scheme reaches: with
+ * edit distance mostly one placement seen many times, at p, p +- 1 .. p +- k
+ * and once per DFS path. With loci on, a call returns one hit per locus: per
+ * query and record, a maximal run of its distinct positions in which each is
+ * at most `window` above the one before; the hit with the least err, ties to
+ * the smaller pos, unchanged. The cut runs on the device, per batch, between
+ * the canonical sort and the download, before --max_hits (which then keeps
+ * the n best loci per query); on a multi-part index per part.
+ * on != 0: every later search call of this context (..._search*,
+ * ..._search_best*, sahara_gpu_run) returns one hit per locus for `window`;
+ * on == 0 (the default) restores the full multiset. A NULL context or NULL
+ * stats is refused with a negative code and a message. */
+int  sahara_gpu_set_loci(void* ctx, int on, uint32_t window);
+typedef struct sahara_loci_stats {     /* 32 B */
+    uint64_t hits_in;    /* hits the stage took (what the call would have returned with loci off, before --max_hits) */
+    uint64_t loci;       /* hits it kept */
+    uint64_t batches;    /* batches it ran on */
+    double   kernel_ms;  /* device time of the stage (HIP events), summed over batches and index parts */
+} sahara_loci_stats;
+/* ... of the context's last search call; zeros if loci were off. */
+int  sahara_gpu_loci_stats(void* ctx, sahara_loci_stats* stats);
+
 /* Device-resident form of the same path for benchmarking: stage patterns and
  * scheme once, run search+locate+sort with results left in HBM, fetch later. */
 int  sahara_gpu_stage(void* ctx, const uint8_t* ranks, uint64_t n_patterns, uint32_t len,

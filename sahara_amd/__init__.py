@@ -97,6 +97,10 @@ class AlignStats(C.Structure):
                 ("total_ms", C.c_double)]
 
 
+class LociStats(C.Structure):
+    _fields_ = [("hits_in", C.c_uint64), ("loci", C.c_uint64), ("batches", C.c_uint64), ("kernel_ms", C.c_double)]
+
+
 EXPORTED = {
     # name: (restype, argtypes)
     "sahara_gpu_last_error": (C.c_char_p, []),
@@ -112,6 +116,8 @@ EXPORTED = {
     "sahara_gpu_export_sa": (C.c_int, [C.c_void_p, u32p]),
     "sahara_gpu_export_text": (C.c_int, [C.c_void_p, u8p]),
     "sahara_gpu_set_mode": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "sahara_gpu_set_loci": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
+    "sahara_gpu_loci_stats": (C.c_int, [C.c_void_p, C.POINTER(LociStats)]),
     "sahara_gpu_select_part": (C.c_int, [C.c_void_p, C.c_uint32]),
     "sahara_gpu_part_info": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     "sahara_gpu_search": (C.c_int, [C.c_void_p, u8p, C.c_uint64, C.c_uint32, u32p, u32p, u32p,
@@ -324,6 +330,25 @@ class BiFMIndex:
         """verify: continue singleton intervals against the resident text;
         locate_sa: locate through the resident full SA (else LF walks)."""
         _check(lib().sahara_gpu_set_mode(self._h, int(verify), int(locate_sa)))
+
+    def set_loci(self, window):
+        """Loci (docs/semantics.md "Loci"): with an int, every later search call
+        on this index returns one hit per locus for that window (positions of
+        one query in one record chained while each is at most `window` above
+        the one before; the hit with the least err, ties to the smaller pos);
+        None restores the full multiset. The setting stays until changed."""
+        if window is None:
+            _check(lib().sahara_gpu_set_loci(self._h, 0, 0))
+            return
+        if int(window) < 0 or int(window) > 0xFFFFFFFF:
+            raise ValueError("loci window must be in [0, 2^32)")
+        _check(lib().sahara_gpu_set_loci(self._h, 1, int(window)))
+
+    def loci_stats(self):
+        """Figures of the loci stage in the last search call (zeros if loci were off)."""
+        s = LociStats()
+        _check(lib().sahara_gpu_loci_stats(self._h, C.byref(s)))
+        return {n: getattr(s, n) for n, _ in s._fields_}
 
     # ---- device-resident path (bench) ----
     def stage(self, queries, scheme, edit=True):

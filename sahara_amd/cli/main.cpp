@@ -444,9 +444,11 @@ int cmdSearch(int argc, char** argv) {
     Opt maxHits{{"--max_hits"}, false, "0"}, limit{{"--limit_queries"}};
     Opt gpus{{"--gpus"}, false, "1"}, emitErr{{"--emit-errors"}, true}, fmOnly{{"--fm-only"}, true};
     Opt emitCigar{{"--emit-cigar"}, true};
+    // one hit per locus (docs/semantics.md "Loci"): --loci with the window W = -e's value, --loci-window <n> with W = n
+    Opt loci{{"--loci"}, true}, lociWindow{{"--loci-window"}};
     Parser p;
     for (Opt* o : {&query, &index, &output, &gen, &dyn, &errors, &noRev, &mode, &dist, &maxHits, &limit, &gpus,
-                   &emitErr, &fmOnly, &emitCigar})
+                   &emitErr, &fmOnly, &emitCigar, &loci, &lociWindow})
         p.add(*o);
     p.parse(argc, argv, 2);
     if (!p.positional.empty()) throw CliError("unexpected argument " + p.positional[0]);
@@ -459,6 +461,9 @@ int cmdSearch(int argc, char** argv) {
     const int k = (int)toU64(errors.value, "--errors");
     const long mh = std::strtol(maxHits.value.c_str(), nullptr, 10);
     const uint32_t ngpu = (uint32_t)std::max<uint64_t>(1, toU64(gpus.value, "--gpus"));
+    const bool lociOn = loci.given || lociWindow.given;
+    const uint64_t lociW = lociWindow.given ? toU64(lociWindow.value, "--loci-window") : (uint64_t)k;
+    if (lociOn && lociW > 0xFFFFFFFFull) throw CliError("--loci-window is at most 4294967295");
     if (emitCigar.given && k > SAHARA_ALIGN_MAX_ERR)
         throw CliError("--emit-cigar aligns at most " + std::to_string(SAHARA_ALIGN_MAX_ERR) + " errors (-e)");
 
@@ -568,6 +573,8 @@ int cmdSearch(int argc, char** argv) {
         if (!loadErrs[g].empty()) throw CliError("loading index: " + loadErrs[g]);
     if (fmOnly.given)
         for (void* c : ctx) check(sahara_gpu_set_mode(c, 0, 0), "set mode");
+    if (lociOn)  // every shard's context: shards split by query, a locus lies within one query
+        for (void* c : ctx) check(sahara_gpu_set_loci(c, 1, (uint32_t)lociW), "set loci");
     sahara_index_info info{};
     check(sahara_gpu_index_info(ctx[0], &info), "index info");
     timing.emplace_back("ld index", sw.reset());
@@ -659,6 +666,7 @@ int cmdSearch(int argc, char** argv) {
     std::vector<HitPart> parts(ngpu);
     std::vector<double> devLocate(ngpu, 0.0), devSearch(ngpu, 0.0), devAlign(ngpu, 0.0);
     std::vector<std::string> errs(ngpu);
+    std::vector<sahara_loci_stats> devLoci(ngpu);
     {
         std::vector<std::thread> th;
         for (uint32_t g = 0; g < ngpu; ++g) {
@@ -707,6 +715,7 @@ int cmdSearch(int argc, char** argv) {
                 sahara_stats st{};
                 sahara_gpu_stats(ctx[g], &st);
                 devLocate[g] = (st.locate_ms + st.sort_ms) / 1e3;
+                if (lociOn) sahara_gpu_loci_stats(ctx[g], &devLoci[g]);
                 devSearch[g] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
                 part.hits = hits;
                 part.n = nh;
@@ -771,6 +780,11 @@ int cmdSearch(int argc, char** argv) {
     std::printf("  total time:          %10.2fs\n", total);
     std::printf("  queries per second:  %10.0fq/s\n", (double)nq / total);
     std::printf("  number of hits:      %10llu\n", (unsigned long long)nhits);
+    if (lociOn) {
+        unsigned long long in = 0, kept = 0;
+        for (const sahara_loci_stats& s : devLoci) in += s.hits_in, kept += s.loci;
+        std::printf("  loci:                %llu of %llu hits\n", kept, in);
+    }
     // the index loads beside the query ingest: "ld index" above is the part of
     // its load the ingest did not hide; this is its whole load
     std::printf("  index load:          %10.2fs (beside ld queries)\n",
@@ -815,6 +829,7 @@ void help() {
         "  sahara search -q <fasta> -i <index> [-o <out>] [-g <generator>] [-e <k>] [--no-reverse]\n"
         "                [-m all|besthits] [-d ham|lev] [--max_hits <n>] [--limit_queries <n>]\n"
         "                [--gpus <N>] [--emit-errors] [--emit-cigar] [--fm-only]\n"
+        "                [--loci] [--loci-window <n>]   one hit per locus (window: -e's value, or n)\n"
         "  sahara read_simulator -o <fasta> [-i <reference>] [-l <len>] [-n <reads>] [-e <errors>]\n"
         "                [--substitution_errors n] [--insertion_errors n] [--deletion_errors n]\n"
         "                [--fasta_line_length n] [--seed s]\n"

@@ -413,6 +413,9 @@ struct BlockRecs {
         c->sk.route = HitRoute::Records;
         c->sk.host = pinned ? recs.get() : nullptr;
         c->sk.cap = pinned ? capBytes / 8 : 0;
+        // SAHARA_SINK_RECORDS: the sink takes no more records than this during the pass (a test hook: pinned
+        // buffers come in 2 MB steps, so a small call's sink is never too small, and collect's refill never runs)
+        if (const char* e = std::getenv("SAHARA_SINK_RECORDS")) c->sk.cap = std::min<uint64_t>(c->sk.cap, std::strtoull(e, nullptr, 10));
         if (c->sk.cap) c->reserveRecs(c->sk.cap);
         recCap = capBytes / 8;
     }
@@ -536,6 +539,7 @@ static void bestOnHost(Ctx* c, const uint8_t* ranks, uint64_t n_patterns, uint32
     std::vector<uint8_t> sub;
     std::vector<sahara_hit> all;
     sahara_stats acc{};
+    sahara_loci_stats lociAcc{};  // (each pass below is a run of its own: the call's figures are their sums)
     uint64_t off = 0;
     for (uint32_t j = 0; j < sc.n && !todo.empty(); off += (uint64_t)sc.ns[j] * len, ++j) {
         const uint8_t* src = ranks;
@@ -561,6 +565,10 @@ static void bestOnHost(Ctx* c, const uint8_t* ranks, uint64_t n_patterns, uint32
         acc.total_ms += c->stats.total_ms;
         acc.hits += c->stats.hits;
         acc.patterns += c->stats.patterns;
+        lociAcc.hits_in += c->loci.stats.hits_in;
+        lociAcc.loci += c->loci.stats.loci;
+        lociAcc.batches += c->loci.stats.batches;
+        lociAcc.kernel_ms += c->loci.stats.kernel_ms;
         std::vector<char> found(todo.size(), 0);
         for (auto& h : v) {
             found[h.qid] = 1;
@@ -573,6 +581,7 @@ static void bestOnHost(Ctx* c, const uint8_t* ranks, uint64_t n_patterns, uint32
         todo.resize(w);
     }
     c->stats = acc;
+    c->loci.stats = lociAcc;
     std::sort(all.begin(), all.end(), hitLess);
     if (max_hits) limitHits(all, max_hits);
     handOver(all, hits, n_hits);

@@ -124,7 +124,7 @@ Ctx* newCtx(int device) {
     // memory-bound kernels on the other streams ran 1.4-1.8x longer, r5.)
     for (Stream* s : {&c->st, &c->stB, &c->stC, &c->stD, &c->stE, &c->stF}) *s = Stream(hipStreamNonBlocking);
     for (Event* e : {&c->outCopied[0], &c->outCopied[1], &c->locStart, &c->locDone, &c->sortDone, &c->totalsDown,
-                     &c->flagsDown, &c->recsMade})
+                     &c->flagsDown, &c->recsMade, &c->lociStart, &c->lociDone})
         *e = Event(hipEventDefault);
     for (Event* e : {&c->totalsDownSleep, &c->flagsDownSleep}) *e = Event(hipEventDisableTiming | hipEventBlockingSync);
     for (auto& e : c->ringEv) e = Event(hipEventDisableTiming);
@@ -330,6 +330,21 @@ int sahara_gpu_set_mode(void* ctx, int verify, int locate_sa) {
         Ctx* c = ctxOf(ctx);
         c->verify = verify != 0;
         c->locateSA = locate_sa != 0;
+    });
+}
+
+int sahara_gpu_set_loci(void* ctx, int on, uint32_t window) {
+    return guarded([&] {
+        Ctx* c = ctxOf(ctx);
+        c->loci.on = on != 0;
+        c->loci.window = on ? window : 0u;
+    });
+}
+
+int sahara_gpu_loci_stats(void* ctx, sahara_loci_stats* stats) {
+    return guarded([&] {
+        if (!stats) throw Error("sahara_gpu_loci_stats: null output");
+        *stats = ctxOf(ctx)->loci.stats;
     });
 }
 

@@ -325,6 +325,17 @@ struct Ctx {
     DevBuf<uint32_t> limitCnt;            // limitBatch's buffers (sk.limitN)
     DevBuf<uint64_t> limitOff;
     DevBuf<sahara_hit> limitBuf;
+    // The loci stage (docs/semantics.md "Loci"; loci.hip): a setting of the
+    // context, not of a call (sahara_gpu_set_loci): when on, every batch of
+    // every pass cuts its whole hits to one record per locus right after the
+    // sort (pass.cpp finish). stats: of the last search call, summed over its
+    // batches, parts and host besthits passes.
+    struct Loci {
+        bool on = false;
+        uint32_t window = 0;
+        sahara_loci_stats stats{};
+        LociBufs bufs;
+    } loci;
     // SAHARA_TIMING=2: host-side marks of one call (ms since its start, what)
     bool traceOn = false;
     std::chrono::steady_clock::time_point traceT0;
@@ -394,6 +405,7 @@ struct Ctx {
     // sort + decode done (timing), the batch's totals and its locate flags
     // in the pinned record, its compact records made
     Event locStart, locDone, sortDone, totalsDown, flagsDown, recsMade;
+    Event lociStart, lociDone;  // around a batch's loci stage on stC (sahara_loci_stats.kernel_ms)
     // the finisher's waits in a streamed call, recorded in place of totalsDown
     // and beside flagsDown: blocking-sync events, so that it sleeps instead of
     // spinning a CPU that the packing threads need (a 16-CPU quota on the GPU box)

@@ -23,7 +23,14 @@ DeviceIndex& partOf(Ctx* c, uint32_t p) { return p == 0 ? c->I : c->more.at(p - 
 // the whole index iff its interval is non-empty in some part, and its rows
 // are the union of its rows over the parts. Hits reach the
 // host after the last part (no per-batch sink).
+// Loci on a multi-part index: the stage runs per part, inside each part's
+// pass (Pass::finish), on the part's own record ids. A locus lies within one
+// record and a record lies wholly in one part, so the loci of the merged hits
+// are the union of the parts' loci, each with the same records in the same
+// order: filtering per part equals filtering after the merge, and the merge
+// moves a tenth of the records.
 void run(Ctx* c, bool count) {
+    c->loci.stats = sahara_loci_stats{};  // of this call: the passes below add to them
     if (c->more.empty()) return runOne(c, count);
     // (rounds mask a query by its rows in one part; "found" is decided across the parts: capi.cpp bestOnHost)
     if (c->rounds.size() > 1) throw Error("a pass of several rounds needs a single-part index");
@@ -84,9 +91,11 @@ void runOne(Ctx* c, bool count) {
     auto t0 = std::chrono::steady_clock::now();
     sahara_stats S{};
     bool overflow = false;
+    const sahara_loci_stats lociBefore = c->loci.stats;  // (a multi-part call's earlier parts)
     runPass(c, count, false, S, overflow);
     if (overflow) {
         S = sahara_stats{};
+        c->loci.stats = lociBefore;  // the batches finished before the overflow are redone
         runPass(c, count, true, S, overflow);
     }
     S.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -365,6 +374,7 @@ struct Pass {
     bool& overflow;
     hipStream_t sA, sB, sC, sD;          // FM phase; text; locate / sort; seeds (serial: all Ctx::st)
     uint32_t seenTask = 0, seenHit = 0;  // pipelined overflow: the caps the re-run needs
+    bool lociRan = false;                // the batch just finished ran the loci stage (finishCheck reads its span)
 
     Ctx::Slot& slotOf(uint64_t b) const { return c->slot[b % Ctx::kSlots]; }
 
@@ -615,7 +625,7 @@ struct Pass {
         // Where the batch goes is decided here, once (hit_route.h).
         auto decide = [&](uint64_t r) {
             return decideBatch({c->sk.route, c->sk.wholeFallback, c->sk.ok, c->nout, r, nb, c->sk.cap, c->sk.limitN,
-                                c->more.empty(), Ctx::kDownSlot});
+                                c->more.empty(), Ctx::kDownSlot, c->loci.on});
         };
         BatchPlan d = decide(rows);
         const uint64_t end = c->nout + rows;
@@ -634,6 +644,21 @@ struct Pass {
             sortDecode(c->k0.ptr, c->k1.ptr, rows, c->qoff.ptr, (uint32_t)nb, c->big.ptr, nbig, c->huge.ptr, nhuge, q0,
                        c->I.dRecStarts.ptr, (uint32_t)c->I.recStarts.size(), c->out.ptr + c->nout, c->tmp.ptr,
                        c->tmp.cap, sC);
+        }
+        // Loci (docs/semantics.md "Loci"): the batch's whole hits, sorted, cut
+        // to one record per locus where they lie; everything after it (the
+        // --max_hits cut, the copies, the sink) sees the representatives only.
+        lociRan = c->loci.on && rows != 0;
+        if (lociRan) {
+            sahara_loci_stats& L = c->loci.stats;
+            L.hits_in += rows;
+            ++L.batches;
+            SH_HIP(hipEventRecord(c->lociStart, sC));
+            rows = lociBatch(c->out.ptr + c->nout, rows, c->loci.window, c->sk.limitN ? c->qoff.ptr : nullptr,
+                             (uint32_t)nb, q0, c->loci.bufs, c->limitBuf, c->tmp, &rec.kept, sC);
+            SH_HIP(hipEventRecord(c->lociDone, sC));
+            L.loci += rows;
+            d = decide(rows);  // (never direct, as below)
         }
         if (c->sk.limitN) {  // --max_hits: this batch's queries keep their n best positions (search_n)
             rows = limitBatch(c->out.ptr + c->nout, rows, c->qoff.ptr, (uint32_t)nb, c->sk.limitN, c->limitCnt,
@@ -712,6 +737,10 @@ struct Pass {
         S.locate_ms += ms;
         SH_HIP(hipEventElapsedTime(&ms, c->locDone, c->sortDone));
         S.sort_ms += ms;
+        if (lociRan) {
+            SH_HIP(hipEventElapsedTime(&ms, c->lociStart, c->lociDone));
+            c->loci.stats.kernel_ms += ms;
+        }
         c->mark("checked", b);
     }
 };

@@ -104,19 +104,19 @@ constexpr uint32_t kQueueWords = 256;
 enum QueueAt : uint32_t { kQueueSeeds = 0, kQueueSeedTasks = kQueueWords, kQueueFmTasks = 2 * kQueueWords,
                          kQueuesWords = 3 * kQueueWords };
 // One batch's record in pinned host memory (Ctx::pinned), written by
-// kBatchTotals (words 0-11), kLocateFlagsOut (7) and limitBatch (12-13)
+// kBatchTotals (words 0-11), kLocateFlagsOut (7), lociBatch and limitBatch (12-13, one after the other)
 struct BatchRecord {
     uint32_t slot[7];      // the slot's counters, by SlotWord
     uint32_t locateFlags;  // the locate chain's flags word (kFlagLocate)
     uint64_t rows;         // the batch's row total
     uint32_t nbig, nhuge;  // long / huge segments
-    uint64_t kept;         // rows --max_hits keeps
+    uint64_t kept;         // rows the loci stage keeps, then rows --max_hits keeps (each read before the next is written)
     uint32_t pad[2];
 };
 static_assert(sizeof(BatchRecord) == 64 && offsetof(BatchRecord, slot) == 0 &&
               offsetof(BatchRecord, locateFlags) == 4 * 7 && offsetof(BatchRecord, rows) == 4 * kSlotWords &&
               offsetof(BatchRecord, nbig) == 4 * 10 && offsetof(BatchRecord, nhuge) == 4 * 11 &&
-              offsetof(BatchRecord, kept) == 4 * 12, "BatchRecord is what kBatchTotals and limitBatch write");
+              offsetof(BatchRecord, kept) == 4 * 12, "BatchRecord is what kBatchTotals, lociBatch and limitBatch write");
 
 // work counters of count mode (sahara_stats; Ctx::counters)
 constexpr uint32_t kCounters = 56;
@@ -275,5 +275,15 @@ void launchCompactHits(const sahara_hit* h, uint64_t n, uint64_t qidBase, const 
 // compact records of one batch (first qid qidBase) back into whole hits
 void launchExpandRecs(const uint64_t* recs, uint64_t n, uint64_t qidBase, const uint64_t* starts, uint32_t nrec,
                       sahara_hit* out, hipStream_t st);
+
+// ---- loci.hip: one batch's whole hits cut to one record per locus (docs/semantics.md "Loci")
+struct LociBufs {
+    DevBuf<uint32_t> flag, num;  // per record: starts a locus; its locus + 1 (the flags' inclusive sum)
+    DevBuf<unsigned long long> best;  // per locus: the least (err, index) key
+};
+// in place, kept records returned (host-synchronous, as limitBatch); qoff != nullptr: the batch's
+// per-query segments rewritten for the records kept (what limitBatch reads next)
+uint64_t lociBatch(sahara_hit* out, uint64_t rows, uint32_t window, uint64_t* qoff, uint32_t nq, uint64_t qidBase,
+                   LociBufs& B, DevBuf<sahara_hit>& buf, DevBuf<char>& tmp, uint64_t* hostKept, hipStream_t st);
 
 }  // namespace sahara
