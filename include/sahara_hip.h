@@ -326,6 +326,38 @@ typedef struct sahara_loci_stats {     /* 32 B */
 /* ... of the context's last search call; zeros if loci were off. */
 int  sahara_gpu_loci_stats(void* ctx, sahara_loci_stats* stats);
 
+/* --- pairs (docs/semantics.md "Pairs") ---
+ * Paired-end reads, interleaved: read 2p is mate A of pair p and read 2p + 1
+ * its mate B, so that with the reverse complements pair p owns the qids 4p
+ * (A), 4p + 1 (rc A), 4p + 2 (B) and 4p + 3 (rc B); the partner of qid q is
+ * q ^ 3. A hit of an even qid at (s, a) and one of its partner at (s', b) are
+ * concordant iff s == s' and the fragment b + len - a lies in
+ * [max(min_fragment, len), max_fragment] (len: the call's pattern length).
+ * With pairs on, a call returns the hits that have a concordant mate among
+ * the call's hits, unchanged and in canonical order. The cut runs on the
+ * device, per batch, after the loci stage (if on) and before --max_hits; on a
+ * multi-part index per part.
+ * on != 0: every later search call of this context is filtered so; on == 0
+ * (the default) restores every hit. Refused with a negative code and a
+ * message: a NULL context, min_fragment > max_fragment, NULL stats. With
+ * pairs on a search call is refused before any device work if max_fragment
+ * is below its pattern length, if its number of patterns (after `limit`) is
+ * no multiple of 4, if it is a reads or packed call with reverse == 0, or if
+ * it is a besthits call that runs as a host loop of one pass per scheme (a
+ * multi-part index, SAHARA_BEST_HOST=1). Calls that take the caller's own
+ * patterns (sahara_gpu_search, _search_best, _stage) leave the grouping by
+ * four to the caller. */
+int  sahara_gpu_set_pairs(void* ctx, int on, uint32_t min_fragment, uint32_t max_fragment);
+typedef struct sahara_pairs_stats {    /* 40 B */
+    uint64_t hits_in;    /* hits the stage took (after the loci stage, before --max_hits) */
+    uint64_t kept;       /* hits it kept */
+    uint64_t pairs;      /* pairs with a kept hit */
+    uint64_t batches;    /* batches it ran on */
+    double   kernel_ms;  /* device time of the stage (HIP events), summed over batches and index parts */
+} sahara_pairs_stats;
+/* ... of the context's last search call; zeros if pairs were off. */
+int  sahara_gpu_pairs_stats(void* ctx, sahara_pairs_stats* stats);
+
 /* Device-resident form of the same path for benchmarking: stage patterns and
  * scheme once, run search+locate+sort with results left in HBM, fetch later. */
 int  sahara_gpu_stage(void* ctx, const uint8_t* ranks, uint64_t n_patterns, uint32_t len,

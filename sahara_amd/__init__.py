@@ -101,6 +101,11 @@ class LociStats(C.Structure):
     _fields_ = [("hits_in", C.c_uint64), ("loci", C.c_uint64), ("batches", C.c_uint64), ("kernel_ms", C.c_double)]
 
 
+class PairsStats(C.Structure):
+    _fields_ = [("hits_in", C.c_uint64), ("kept", C.c_uint64), ("pairs", C.c_uint64), ("batches", C.c_uint64),
+                ("kernel_ms", C.c_double)]
+
+
 EXPORTED = {
     # name: (restype, argtypes)
     "sahara_gpu_last_error": (C.c_char_p, []),
@@ -118,6 +123,8 @@ EXPORTED = {
     "sahara_gpu_set_mode": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "sahara_gpu_set_loci": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
     "sahara_gpu_loci_stats": (C.c_int, [C.c_void_p, C.POINTER(LociStats)]),
+    "sahara_gpu_set_pairs": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32]),
+    "sahara_gpu_pairs_stats": (C.c_int, [C.c_void_p, C.POINTER(PairsStats)]),
     "sahara_gpu_select_part": (C.c_int, [C.c_void_p, C.c_uint32]),
     "sahara_gpu_part_info": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     "sahara_gpu_search": (C.c_int, [C.c_void_p, u8p, C.c_uint64, C.c_uint32, u32p, u32p, u32p,
@@ -348,6 +355,29 @@ class BiFMIndex:
         """Figures of the loci stage in the last search call (zeros if loci were off)."""
         s = LociStats()
         _check(lib().sahara_gpu_loci_stats(self._h, C.byref(s)))
+        return {n: getattr(s, n) for n, _ in s._fields_}
+
+    def set_pairs(self, min_fragment, max_fragment=None):
+        """Pairs (docs/semantics.md "Pairs"): with two ints, every later search
+        call on this index takes its reads as interleaved mate pairs (read 2p
+        and read 2p + 1) and returns only the hits that have a concordant
+        mate: on the same record, the forward mate left of the reverse one,
+        the fragment in [max(min_fragment, len), max_fragment].
+        set_pairs(None) restores every hit. The setting stays until changed."""
+        if min_fragment is None:
+            _check(lib().sahara_gpu_set_pairs(self._h, 0, 0, 0))
+            return
+        if max_fragment is None:
+            raise ValueError("set_pairs takes min_fragment and max_fragment, or None")
+        lo, hi = int(min_fragment), int(max_fragment)
+        if not (0 <= lo <= 0xFFFFFFFF and 0 <= hi <= 0xFFFFFFFF):
+            raise ValueError("fragment lengths must be in [0, 2^32)")
+        _check(lib().sahara_gpu_set_pairs(self._h, 1, lo, hi))
+
+    def pairs_stats(self):
+        """Figures of the pair stage in the last search call (zeros if pairs were off)."""
+        s = PairsStats()
+        _check(lib().sahara_gpu_pairs_stats(self._h, C.byref(s)))
         return {n: getattr(s, n) for n, _ in s._fields_}
 
     # ---- device-resident path (bench) ----

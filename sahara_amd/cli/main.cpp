@@ -446,9 +446,12 @@ int cmdSearch(int argc, char** argv) {
     Opt emitCigar{{"--emit-cigar"}, true};
     // one hit per locus (docs/semantics.md "Loci"): --loci with the window W = -e's value, --loci-window <n> with W = n
     Opt loci{{"--loci"}, true}, lociWindow{{"--loci-window"}};
+    // paired-end reads, the mates interleaved in the query file (docs/semantics.md "Pairs"): only hits with a
+    // concordant mate are written
+    Opt paired{{"--paired"}, true}, minFrag{{"--min-fragment"}, false, "0"}, maxFrag{{"--max-fragment"}, false, "500"};
     Parser p;
     for (Opt* o : {&query, &index, &output, &gen, &dyn, &errors, &noRev, &mode, &dist, &maxHits, &limit, &gpus,
-                   &emitErr, &fmOnly, &emitCigar, &loci, &lociWindow})
+                   &emitErr, &fmOnly, &emitCigar, &loci, &lociWindow, &paired, &minFrag, &maxFrag})
         p.add(*o);
     p.parse(argc, argv, 2);
     if (!p.positional.empty()) throw CliError("unexpected argument " + p.positional[0]);
@@ -464,6 +467,16 @@ int cmdSearch(int argc, char** argv) {
     const bool lociOn = loci.given || lociWindow.given;
     const uint64_t lociW = lociWindow.given ? toU64(lociWindow.value, "--loci-window") : (uint64_t)k;
     if (lociOn && lociW > 0xFFFFFFFFull) throw CliError("--loci-window is at most 4294967295");
+    const uint64_t fragLo = toU64(minFrag.value, "--min-fragment"), fragHi = toU64(maxFrag.value, "--max-fragment");
+    if ((minFrag.given || maxFrag.given) && !paired.given) throw CliError("--min-fragment / --max-fragment need --paired");
+    if (paired.given) {
+        if (noRev.given) throw CliError("--paired needs the reverse complements: it cannot go with --no-reverse");
+        if (fragLo > fragHi) throw CliError("--min-fragment is above --max-fragment");
+        if (fragHi > 0xFFFFFFFFull) throw CliError("--max-fragment is at most 4294967295");
+        if (limit.given && toU64(limit.value, "--limit_queries") % 4)
+            throw CliError("--paired: --limit_queries must be a multiple of 4 (a pair is two mates and their reverse "
+                           "complements)");
+    }
     if (emitCigar.given && k > SAHARA_ALIGN_MAX_ERR)
         throw CliError("--emit-cigar aligns at most " + std::to_string(SAHARA_ALIGN_MAX_ERR) + " errors (-e)");
 
@@ -546,6 +559,15 @@ int cmdSearch(int argc, char** argv) {
     if (limit.given) nq = std::min<size_t>(toU64(limit.value, "--limit_queries"), nq);
     if (nq == 0) throw CliError("query file " + query.value + " was empty - abort\n");
     const size_t nreads = (nq + per - 1) / per;  // reads that contribute a query
+    if (paired.given) {
+        if (nrec % 2)
+            throw CliError("--paired: " + query.value + " holds " + std::to_string(nrec) +
+                           " reads, an odd number: the mates of a pair come one after the other");
+        const uint64_t len0 = Q.f.offs[1] - Q.f.offs[0];
+        if (fragHi < len0)
+            throw CliError("--paired: --max-fragment " + std::to_string(fragHi) + " is below the read length " +
+                           std::to_string(len0));
+    }
     timing.emplace_back("ld queries", sw.reset());
 
     std::printf(
@@ -575,6 +597,8 @@ int cmdSearch(int argc, char** argv) {
         for (void* c : ctx) check(sahara_gpu_set_mode(c, 0, 0), "set mode");
     if (lociOn)  // every shard's context: shards split by query, a locus lies within one query
         for (void* c : ctx) check(sahara_gpu_set_loci(c, 1, (uint32_t)lociW), "set loci");
+    if (paired.given)  // every shard's context: shards split at whole pairs (shard.h)
+        for (void* c : ctx) check(sahara_gpu_set_pairs(c, 1, (uint32_t)fragLo, (uint32_t)fragHi), "set pairs");
     sahara_index_info info{};
     check(sahara_gpu_index_info(ctx[0], &info), "index info");
     timing.emplace_back("ld index", sw.reset());
@@ -667,11 +691,12 @@ int cmdSearch(int argc, char** argv) {
     std::vector<double> devLocate(ngpu, 0.0), devSearch(ngpu, 0.0), devAlign(ngpu, 0.0);
     std::vector<std::string> errs(ngpu);
     std::vector<sahara_loci_stats> devLoci(ngpu);
+    std::vector<sahara_pairs_stats> devPairs(ngpu);
     {
         std::vector<std::thread> th;
         for (uint32_t g = 0; g < ngpu; ++g) {
             th.emplace_back([&, g] {
-                const QueryShard sh = queryShard(nq, per, ngpu, g);
+                const QueryShard sh = queryShard(nq, per, ngpu, g, paired.given ? 2 : 1);
                 const size_t r0 = sh.r0, r1 = sh.r1, q0 = sh.q0, q1 = sh.q1;
                 if (r0 == r1) return;
                 const auto t0 = std::chrono::steady_clock::now();
@@ -716,6 +741,7 @@ int cmdSearch(int argc, char** argv) {
                 sahara_gpu_stats(ctx[g], &st);
                 devLocate[g] = (st.locate_ms + st.sort_ms) / 1e3;
                 if (lociOn) sahara_gpu_loci_stats(ctx[g], &devLoci[g]);
+                if (paired.given) sahara_gpu_pairs_stats(ctx[g], &devPairs[g]);
                 devSearch[g] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
                 part.hits = hits;
                 part.n = nh;
@@ -785,6 +811,11 @@ int cmdSearch(int argc, char** argv) {
         for (const sahara_loci_stats& s : devLoci) in += s.hits_in, kept += s.loci;
         std::printf("  loci:                %llu of %llu hits\n", kept, in);
     }
+    if (paired.given) {
+        unsigned long long in = 0, kept = 0, np = 0;
+        for (const sahara_pairs_stats& s : devPairs) in += s.hits_in, kept += s.kept, np += s.pairs;
+        std::printf("  pairs:               %llu of %llu hits, %llu pairs\n", kept, in, np);
+    }
     // the index loads beside the query ingest: "ld index" above is the part of
     // its load the ingest did not hide; this is its whole load
     std::printf("  index load:          %10.2fs (beside ld queries)\n",
@@ -830,6 +861,8 @@ void help() {
         "                [-m all|besthits] [-d ham|lev] [--max_hits <n>] [--limit_queries <n>]\n"
         "                [--gpus <N>] [--emit-errors] [--emit-cigar] [--fm-only]\n"
         "                [--loci] [--loci-window <n>]   one hit per locus (window: -e's value, or n)\n"
+        "                [--paired] [--min-fragment <n>] [--max-fragment <n>]   the query file holds mate pairs\n"
+        "                interleaved; only hits with a concordant mate are written (fragment 0..500, or n)\n"
         "  sahara read_simulator -o <fasta> [-i <reference>] [-l <len>] [-n <reads>] [-e <errors>]\n"
         "                [--substitution_errors n] [--insertion_errors n] [--deletion_errors n]\n"
         "                [--fasta_line_length n] [--seed s]\n"

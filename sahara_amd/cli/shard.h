@@ -17,12 +17,15 @@ struct QueryShard {
     size_t q0 = 0, q1 = 0;  // their queries [q0, q1) of the interleaved list: qid offset q0, limit q1 - q0
 };
 
-// nq = queries after the cut, per = patterns per read (2 with reverse complements, else 1)
-inline QueryShard queryShard(size_t nq, size_t per, unsigned devices, unsigned g) {
+// nq = queries after the cut, per = patterns per read (2 with reverse complements, else 1);
+// granularity: the reads that stay on one device together (--paired: 2, a pair's mates; the
+// shards then split at multiples of it)
+inline QueryShard queryShard(size_t nq, size_t per, unsigned devices, unsigned g, size_t granularity = 1) {
     const size_t nreads = (nq + per - 1) / per;  // reads that contribute a query
+    const size_t ngroups = (nreads + granularity - 1) / granularity;
     QueryShard s;
-    s.r0 = nreads * g / devices;
-    s.r1 = nreads * (g + 1) / devices;
+    s.r0 = std::min(nreads, ngroups * g / devices * granularity);
+    s.r1 = std::min(nreads, ngroups * (g + 1) / devices * granularity);
     s.q0 = std::min(nq, per * s.r0);
     s.q1 = std::min(nq, per * s.r1);
     return s;

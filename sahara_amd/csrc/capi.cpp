@@ -255,6 +255,14 @@ ReadRows readRows(int reverse, uint64_t n_reads, uint64_t limit) {
     return {npat, reverse ? (npat + 1) / 2 : npat};
 }
 
+// The pair stage's refusals of a reads or packed call, before anything is staged (docs/semantics.md
+// "Pairs"): the mates' reverse complements are what pairs with them, and the list holds whole pairs.
+static void checkPairsReads(const Ctx* c, int reverse, const ReadRows& R, uint32_t len) {
+    if (!c->pairs.on) return;
+    if (!reverse) throw Error("pairs: a reads call needs reverse != 0 (a mate pairs with its partner's reverse complement)");
+    checkPairsCall(c, R.npat, len);
+}
+
 // Hits (or records) a call's sink is sized for: what the last call found and
 // an eighth more (the bench's steady state), else 2 per pattern
 static uint64_t sinkEstimate(const Ctx* c, uint64_t npat) {
@@ -519,6 +527,7 @@ static void searchBlocks(Ctx* c, const uint8_t* reads, uint64_t n_reads, uint32_
     if (c->I.sigma != 5 && c->I.sigma != 6) throw Error("reverse complements need a dna4 or dna5 index");
     if (!c->more.empty()) throw Error("compact hit records need a single-part index (text < 2^32 symbols)");
     const ReadRows R = readRows(reverse, n_reads, limit);
+    checkPairsReads(c, reverse, R, len);
     for (uint64_t i = 0, n = sc.rows() * len; i < n; ++i)
         if (sc.u[i] > 15) throw Error("compact hit records hold at most 15 errors");
     BlockRecs out{blocks};
@@ -540,6 +549,11 @@ static void bestOnHost(Ctx* c, const uint8_t* ranks, uint64_t n_patterns, uint32
     std::vector<sahara_hit> all;
     sahara_stats acc{};
     sahara_loci_stats lociAcc{};  // (each pass below is a run of its own: the call's figures are their sums)
+    // Pairs: a stratum whose hits all lack a mate would leave its queries "not found" here and let them
+    // fall through to the next scheme, where the rounds of a streamed pass fix the stratum first.
+    if (c->pairs.on)
+        throw Error("pairs: besthits as a host loop of one pass per scheme (a multi-part index, SAHARA_BEST_HOST=1) "
+                    "is not supported with pairs on");
     uint64_t off = 0;
     for (uint32_t j = 0; j < sc.n && !todo.empty(); off += (uint64_t)sc.ns[j] * len, ++j) {
         const uint8_t* src = ranks;
@@ -632,6 +646,8 @@ static void bestStreamed(Ctx* c, const uint8_t* src, uint64_t n_reads, uint32_t 
     if (!sc.n) throw Error("besthits: no schemes");
     const ReadRows R = interleave ? readRows(reverse, n_reads, limit) : ReadRows{n_reads, n_reads};
     if (R.npat == 0) throw Error("no patterns");
+    if (interleave) checkPairsReads(c, reverse, R, len);
+    else checkPairsCall(c, R.npat, len);
     const bool rc = interleave && reverse != 0;
     if (c->more.empty() && !bestHostForced()) {
         if (interleave && !packed && c->I.sigma != 5 && c->I.sigma != 6)
@@ -649,7 +665,10 @@ extern "C" {
 
 int sahara_gpu_stage(void* ctx, const uint8_t* ranks, uint64_t n_patterns, uint32_t len, const uint32_t* pi,
                      const uint32_t* l, const uint32_t* u, uint32_t n_searches, int edit) {
-    return guarded([&] { stage(ctxOf(ctx), ranks, n_patterns, len, pi, l, u, &n_searches, 1, edit); });
+    return guarded([&] {
+        checkPairsCall(ctxOf(ctx), n_patterns, len);
+        stage(ctxOf(ctx), ranks, n_patterns, len, pi, l, u, &n_searches, 1, edit);
+    });
 }
 
 int sahara_gpu_run(void* ctx, int count, uint64_t* n_hits) {
@@ -707,6 +726,7 @@ int sahara_gpu_search(void* ctx, const uint8_t* ranks, uint64_t n_patterns, uint
                       const uint32_t* l, const uint32_t* u, uint32_t n_searches, int edit, uint32_t max_hits,
                       sahara_hit** hits, uint64_t* n_hits) {
     return guarded([&] {
+        checkPairsCall(ctxOf(ctx), n_patterns, len);
         searchWhole(ctxOf(ctx), Queries{ranks, n_patterns, false, n_patterns, len, nullptr},
                     Schemes{pi, l, u, &n_searches, 1, edit}, max_hits, hits, n_hits);
     });
@@ -719,6 +739,7 @@ int sahara_gpu_search_reads(void* ctx, const uint8_t* reads, uint64_t n_reads, u
         Ctx* c = ctxOf(ctx);
         if (c->I.sigma != 5 && c->I.sigma != 6) throw Error("reverse complements need a dna4 or dna5 index");
         const ReadRows R = readRows(reverse, n_reads, limit);
+        checkPairsReads(c, reverse, R, len);
         searchWhole(c, Queries{reads, R.rows, reverse != 0, R.npat, len, nullptr}, Schemes{pi, l, u, &n_searches, 1, edit},
                     max_hits, hits, n_hits);
     });
@@ -742,6 +763,7 @@ int sahara_gpu_search_packed(void* ctx, const uint8_t* codes, uint64_t sym0, con
         Ctx* c = ctxOf(ctx);
         if (!codes || (n_count && !n_pos)) throw Error("sahara_gpu_search_packed: null input");
         const ReadRows R = readRows(reverse, n_reads, limit);
+        checkPairsReads(c, reverse, R, len);
         const PackedReads pk{sym0, n_pos, n_count};
         searchWhole(c, Queries{codes, R.rows, reverse != 0, R.npat, len, &pk}, Schemes{pi, l, u, &n_searches, 1, edit},
                     max_hits, hits, n_hits);

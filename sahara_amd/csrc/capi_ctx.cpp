@@ -124,7 +124,8 @@ Ctx* newCtx(int device) {
     // memory-bound kernels on the other streams ran 1.4-1.8x longer, r5.)
     for (Stream* s : {&c->st, &c->stB, &c->stC, &c->stD, &c->stE, &c->stF}) *s = Stream(hipStreamNonBlocking);
     for (Event* e : {&c->outCopied[0], &c->outCopied[1], &c->locStart, &c->locDone, &c->sortDone, &c->totalsDown,
-                     &c->flagsDown, &c->recsMade, &c->lociStart, &c->lociDone})
+                     &c->flagsDown, &c->recsMade, &c->lociStart, &c->lociDone,
+                     &c->pairsStart, &c->pairsDone})
         *e = Event(hipEventDefault);
     for (Event* e : {&c->totalsDownSleep, &c->flagsDownSleep}) *e = Event(hipEventDisableTiming | hipEventBlockingSync);
     for (auto& e : c->ringEv) e = Event(hipEventDisableTiming);
@@ -345,6 +346,23 @@ int sahara_gpu_loci_stats(void* ctx, sahara_loci_stats* stats) {
     return guarded([&] {
         if (!stats) throw Error("sahara_gpu_loci_stats: null output");
         *stats = ctxOf(ctx)->loci.stats;
+    });
+}
+
+int sahara_gpu_set_pairs(void* ctx, int on, uint32_t min_fragment, uint32_t max_fragment) {
+    return guarded([&] {
+        if (on && min_fragment > max_fragment) throw Error("sahara_gpu_set_pairs: min_fragment is above max_fragment");
+        Ctx* c = ctxOf(ctx);
+        c->pairs.on = on != 0;
+        c->pairs.minFrag = on ? min_fragment : 0u;
+        c->pairs.maxFrag = on ? max_fragment : 0u;
+    });
+}
+
+int sahara_gpu_pairs_stats(void* ctx, sahara_pairs_stats* stats) {
+    return guarded([&] {
+        if (!stats) throw Error("sahara_gpu_pairs_stats: null output");
+        *stats = ctxOf(ctx)->pairs.stats;
     });
 }
 

@@ -336,6 +336,17 @@ struct Ctx {
         sahara_loci_stats stats{};
         LociBufs bufs;
     } loci;
+    // The pair stage (docs/semantics.md "Pairs"; pairs.hip): a setting of the
+    // context as well (sahara_gpu_set_pairs): when on, every batch of every
+    // pass, cut at multiples of four patterns, keeps only its hits with a
+    // concordant mate, after the loci stage and before --max_hits. stats: of
+    // the last search call, summed as the loci's are.
+    struct Pairs {
+        bool on = false;
+        uint32_t minFrag = 0, maxFrag = 0;
+        sahara_pairs_stats stats{};
+        PairsBufs bufs;
+    } pairs;
     // SAHARA_TIMING=2: host-side marks of one call (ms since its start, what)
     bool traceOn = false;
     std::chrono::steady_clock::time_point traceT0;
@@ -406,6 +417,7 @@ struct Ctx {
     // in the pinned record, its compact records made
     Event locStart, locDone, sortDone, totalsDown, flagsDown, recsMade;
     Event lociStart, lociDone;  // around a batch's loci stage on stC (sahara_loci_stats.kernel_ms)
+    Event pairsStart, pairsDone;  // around its pair stage (sahara_pairs_stats.kernel_ms)
     // the finisher's waits in a streamed call, recorded in place of totalsDown
     // and beside flagsDown: blocking-sync events, so that it sleeps instead of
     // spinning a CPU that the packing threads need (a 16-CPU quota on the GPU box)
@@ -526,6 +538,9 @@ ReadRows readRows(int reverse, uint64_t n_reads, uint64_t limit);
 // pass.cpp: one pass over the staged patterns (every part of the index)
 DeviceIndex& partOf(Ctx* c, uint32_t p);
 void run(Ctx* c, bool count);
+// with the pair stage on: what a call of npat patterns of length len must satisfy (throws otherwise);
+// the entry points ask before they stage anything, run() asks again for sahara_gpu_run
+void checkPairsCall(const Ctx* c, uint64_t npat, uint32_t len);
 void runOne(Ctx* c, bool count);
 void runPass(Ctx* c, bool count, bool serial, sahara_stats& S, bool& overflow);
 void growCap(uint32_t& cap, uint32_t seen);

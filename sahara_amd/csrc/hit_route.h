@@ -51,6 +51,7 @@ struct BatchIn {
     bool onePart;          // a single-part index
     uint64_t downSlot;     // bytes of a download ring slot (Ctx::kDownSlot)
     bool loci = false;     // the loci stage runs on the batch's whole hits (loci.hip)
+    bool pairs = false;    // the pair stage runs on them (pairs.hip)
 };
 
 struct BatchPlan {
@@ -63,16 +64,17 @@ struct BatchPlan {
 
 // A compact record holds the batch-local query in 28 bits and the sort can
 // write it only where nothing reads the whole hit on the device afterwards:
-// no loci stage, no --max_hits cut, no merge of parts. loci and limitN != 0
-// each make direct and needRecs independent of rows, so a batch decided again
-// with the rows those stages kept (Pass::finish) cannot contradict its sort.
+// no loci stage, no pair stage, no --max_hits cut, no merge of parts. loci,
+// pairs and limitN != 0 each make direct and needRecs independent of rows, so
+// a batch decided again with the rows those stages kept (Pass::finish) cannot
+// contradict its sort.
 inline BatchPlan decideBatch(const BatchIn& in) {
     constexpr uint64_t kRecQueries = 1ull << 28;
     const bool fits = in.ok && in.route != HitRoute::Device && in.nout + in.rows <= in.cap;
     const bool slotFits = in.rows * sizeof(uint64_t) <= in.downSlot;
     const bool takesRecs = in.route == HitRoute::Records || (in.route == HitRoute::Expander && fits && slotFits);
     BatchPlan d{};
-    d.direct = in.rows && takesRecs && !in.loci && in.limitN == 0 && in.onePart && in.nb < kRecQueries;
+    d.direct = in.rows && takesRecs && !in.loci && !in.pairs && in.limitN == 0 && in.onePart && in.nb < kRecQueries;
     d.needRecs = d.direct || in.route == HitRoute::Records;
     d.copy = BatchCopy::None;
     d.ok = fits;

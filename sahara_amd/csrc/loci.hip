@@ -109,6 +109,14 @@ __global__ void kLociSegments(const sahara_hit* __restrict__ h, uint64_t loci, u
 
 }  // namespace
 
+// qoff[0..nq] over the n sorted records h (kLociSegments): what the loci stage and the pair stage
+// (pairs.hip) each leave for limitBatch when they dropped records
+void launchHitSegments(const sahara_hit* h, uint64_t n, uint64_t qidBase, uint32_t nq, uint64_t* qoff, hipStream_t st) {
+    const uint32_t qblocks = std::min<uint32_t>(nq / 256 + 1, 16384);
+    hipLaunchKernelGGL(kLociSegments, dim3(qblocks), dim3(256), 0, st, h, n, qidBase, nq, qoff);
+    SH_HIP(hipGetLastError());
+}
+
 // One batch's whole hits (out, rows; canonical order) reduced in place to one
 // record per locus for `window`; returns the records kept. Host-synchronous
 // like limitBatch: the count sizes the rest of the batch's chain, and comes
@@ -146,11 +154,7 @@ uint64_t lociBatch(sahara_hit* out, uint64_t rows, uint32_t window, uint64_t* qo
     hipLaunchKernelGGL(kLociGather, dim3(gblocks), dim3(256), 0, st, out, B.best.ptr, loci, buf.ptr);
     SH_HIP(hipGetLastError());
     SH_HIP(hipMemcpyAsync(out, buf.ptr, loci * sizeof(sahara_hit), hipMemcpyDeviceToDevice, st));
-    if (qoff) {
-        const uint32_t qblocks = std::min<uint32_t>(nq / 256 + 1, 16384);
-        hipLaunchKernelGGL(kLociSegments, dim3(qblocks), dim3(256), 0, st, out, loci, qidBase, nq, qoff);
-        SH_HIP(hipGetLastError());
-    }
+    if (qoff) launchHitSegments(out, loci, qidBase, nq, qoff, st);
     return loci;
 }
 

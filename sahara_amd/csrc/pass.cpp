@@ -29,8 +29,25 @@ DeviceIndex& partOf(Ctx* c, uint32_t p) { return p == 0 ? c->I : c->more.at(p - 
 // are the union of the parts' loci, each with the same records in the same
 // order: filtering per part equals filtering after the merge, and the merge
 // moves a tenth of the records.
+// Pairs on a multi-part index: per part in the same way. Two concordant hits
+// lie on one record and a record lies wholly in one part, so a hit has a mate
+// among the merged hits iff it has one among its own part's: the union of the
+// parts' kept hits is the kept hits of the merged call. (A pair may keep hits
+// in several parts: the stats' pairs then count it once per part.)
+void checkPairsCall(const Ctx* c, uint64_t npat, uint32_t len) {
+    if (!c->pairs.on) return;
+    if (c->pairs.maxFrag < len)
+        throw Error("pairs: max_fragment " + std::to_string(c->pairs.maxFrag) + " is below the pattern length " +
+                    std::to_string(len));
+    if (npat % 4)
+        throw Error("pairs: " + std::to_string(npat) + " patterns are no multiple of 4 (a pair is two mates and "
+                    "their reverse complements)");
+}
+
 void run(Ctx* c, bool count) {
     c->loci.stats = sahara_loci_stats{};  // of this call: the passes below add to them
+    c->pairs.stats = sahara_pairs_stats{};
+    if (c->sk.staged) checkPairsCall(c, c->npat, c->m);
     if (c->more.empty()) return runOne(c, count);
     // (rounds mask a query by its rows in one part; "found" is decided across the parts: capi.cpp bestOnHost)
     if (c->rounds.size() > 1) throw Error("a pass of several rounds needs a single-part index");
@@ -92,10 +109,12 @@ void runOne(Ctx* c, bool count) {
     sahara_stats S{};
     bool overflow = false;
     const sahara_loci_stats lociBefore = c->loci.stats;  // (a multi-part call's earlier parts)
+    const sahara_pairs_stats pairsBefore = c->pairs.stats;
     runPass(c, count, false, S, overflow);
     if (overflow) {
         S = sahara_stats{};
         c->loci.stats = lociBefore;  // the batches finished before the overflow are redone
+        c->pairs.stats = pairsBefore;
         runPass(c, count, true, S, overflow);
     }
     S.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -182,7 +201,9 @@ static PassPlan makePlan(Ctx* c, bool count, bool redo) {
     // text 3 + FM 2 883-905M and FM 3 847-890M, alternating runs on one box:
     // 115-131 VGPRs per FM wave leave the SIMDs' registers to the text waves
     // and the locate chain.)
-    P.maxBatch = maxBatchOf(k.batch, c->sk.streaming, c->nsearch, c->sk.route == HitRoute::Records);
+    // (pairs: a pair's four qids stay in one batch, pairs.hip)
+    const uint64_t granularity = c->pairs.on ? 4 : 1;
+    P.maxBatch = maxBatchOf(k.batch, c->sk.streaming, c->nsearch, c->sk.route == HitRoute::Records, granularity);
     const uint64_t batchesHere = (c->npat + P.maxBatch - 1) / P.maxBatch;
     if (!serial && batchesHere > 1 && c->verify) bpc = 1;
     if (k.fmBpc) bpc = (int)std::max<long>(1, std::min<long>(fullBpc, *k.fmBpc));
@@ -230,7 +251,7 @@ static PassPlan makePlan(Ctx* c, bool count, bool redo) {
     // and the pool pack (device-resident runs spin)
     P.sleepy = c->sk.streaming && !serial;
     P.probe = count && k.dump;
-    P.bstart = batchStarts(c->npat, P.maxBatch, k.rampHead, k.rampTail, serial);
+    P.bstart = batchStarts(c->npat, P.maxBatch, k.rampHead, k.rampTail, serial, granularity);
     return P;
 }
 
@@ -375,6 +396,7 @@ struct Pass {
     hipStream_t sA, sB, sC, sD;          // FM phase; text; locate / sort; seeds (serial: all Ctx::st)
     uint32_t seenTask = 0, seenHit = 0;  // pipelined overflow: the caps the re-run needs
     bool lociRan = false;                // the batch just finished ran the loci stage (finishCheck reads its span)
+    bool pairsRan = false;               // ... the pair stage (its span and its pairs count)
 
     Ctx::Slot& slotOf(uint64_t b) const { return c->slot[b % Ctx::kSlots]; }
 
@@ -625,7 +647,7 @@ struct Pass {
         // Where the batch goes is decided here, once (hit_route.h).
         auto decide = [&](uint64_t r) {
             return decideBatch({c->sk.route, c->sk.wholeFallback, c->sk.ok, c->nout, r, nb, c->sk.cap, c->sk.limitN,
-                                c->more.empty(), Ctx::kDownSlot, c->loci.on});
+                                c->more.empty(), Ctx::kDownSlot, c->loci.on, c->pairs.on});
         };
         BatchPlan d = decide(rows);
         const uint64_t end = c->nout + rows;
@@ -654,11 +676,28 @@ struct Pass {
             L.hits_in += rows;
             ++L.batches;
             SH_HIP(hipEventRecord(c->lociStart, sC));
-            rows = lociBatch(c->out.ptr + c->nout, rows, c->loci.window, c->sk.limitN ? c->qoff.ptr : nullptr,
+            // (the segments rewritten for whichever stage reads them next)
+            const bool segments = c->sk.limitN || (c->pairs.on && P.k.pairsNarrow);
+            rows = lociBatch(c->out.ptr + c->nout, rows, c->loci.window, segments ? c->qoff.ptr : nullptr,
                              (uint32_t)nb, q0, c->loci.bufs, c->limitBuf, c->tmp, &rec.kept, sC);
             SH_HIP(hipEventRecord(c->lociDone, sC));
             L.loci += rows;
             d = decide(rows);  // (never direct, as below)
+        }
+        // Pairs (docs/semantics.md "Pairs"): of what is left, the hits with a
+        // concordant mate in the batch, which holds whole pairs (makePlan).
+        pairsRan = c->pairs.on && rows != 0;
+        if (pairsRan) {
+            sahara_pairs_stats& R = c->pairs.stats;
+            R.hits_in += rows;
+            ++R.batches;
+            SH_HIP(hipEventRecord(c->pairsStart, sC));
+            rows = pairsBatch(c->out.ptr + c->nout, rows, c->m, c->pairs.minFrag, c->pairs.maxFrag,
+                              c->sk.limitN || P.k.pairsNarrow ? c->qoff.ptr : nullptr, (uint32_t)nb, q0,
+                              P.k.pairsNarrow, c->sk.limitN != 0, c->pairs.bufs, c->limitBuf, c->tmp, &rec.kept, &rec.pairs, sC);
+            SH_HIP(hipEventRecord(c->pairsDone, sC));
+            R.kept += rows;
+            d = decide(rows);
         }
         if (c->sk.limitN) {  // --max_hits: this batch's queries keep their n best positions (search_n)
             rows = limitBatch(c->out.ptr + c->nout, rows, c->qoff.ptr, (uint32_t)nb, c->sk.limitN, c->limitCnt,
@@ -740,6 +779,11 @@ struct Pass {
         if (lociRan) {
             SH_HIP(hipEventElapsedTime(&ms, c->lociStart, c->lociDone));
             c->loci.stats.kernel_ms += ms;
+        }
+        if (pairsRan) {  // (flagsDown has passed the stage's last copy, the one into the batch's record)
+            SH_HIP(hipEventElapsedTime(&ms, c->pairsStart, c->pairsDone));
+            c->pairs.stats.kernel_ms += ms;
+            c->pairs.stats.pairs += c->pinned.ptr[b].pairs;
         }
         c->mark("checked", b);
     }

@@ -34,7 +34,7 @@ inline std::vector<uint64_t> parseRamp(const char* e) {
 }
 
 struct PassKnobs {
-    bool pipeline, dump, chunkSeeds, kmerPos, seedTasks;
+    bool pipeline, dump, chunkSeeds, kmerPos, seedTasks, pairsNarrow;
     uint32_t fmLdsDepth, fmStealAt, stealAt, split, textSteps, refillAt, pollUs;
     uint32_t hitCap, taskCap;              // 0: unset
     unsigned long timerSlackNs;
@@ -101,6 +101,9 @@ inline PassKnobs readPassKnobs(bool verify) {
     // the hit and task buffers' first sizes (tests force overflow re-runs)
     if (auto v = num("SAHARA_HITCAP")) k.hitCap = (uint32_t)std::max(1L, *v);
     if (auto v = num("SAHARA_TASKCAP")) k.taskCap = (uint32_t)std::max(1L, *v);
+    // the pair stage's lower bounds: 1 within the partner query's segment, 0 (A/B) over the whole batch
+    // (pairs.hip kPairFlags; DESIGN.md §3.10 has both measured)
+    k.pairsNarrow = num("SAHARA_PAIRS_NARROW").value_or(1) != 0;
     k.batch = num("SAHARA_BATCH");        // maxBatchOf
     k.fmBpc = num("SAHARA_FM_BPC");       // workgroups per CU (pass.cpp makePlan)
     k.textBpc = num("SAHARA_TEXT_BPC");
@@ -114,12 +117,16 @@ inline PassKnobs readPassKnobs(bool verify) {
 // download, so smaller ones shorten both ends; C3 compact reads path
 // 584-615M -> 668-689M reads/s, profiles/r03_pcie_batch_sweep.txt),
 // fewer for schemes with many searches (work items must fit 2^31);
-// SAHARA_BATCH (`batch`) sets it (tests of the pipeline)
-inline uint64_t maxBatchOf(std::optional<long> batch, bool streaming, uint32_t nsearch, bool compactRecs) {
+// SAHARA_BATCH (`batch`) sets it (tests of the pipeline). granularity g > 1
+// (the pair stage: 4, a pair's qids stay in one batch): rounded down to a
+// multiple of g, and g where that leaves nothing (one group per batch).
+inline uint64_t maxBatchOf(std::optional<long> batch, bool streaming, uint32_t nsearch, bool compactRecs,
+                           uint64_t granularity = 1) {
     const uint64_t most = (1ull << 31) / nsearch;
     uint64_t mb = std::min<uint64_t>(streaming ? 1ull << 21 : 1ull << 22, most);
     if (batch) mb = std::max<uint64_t>(1, std::min<uint64_t>(most, (uint64_t)*batch));
-    return compactRecs ? std::min<uint64_t>(mb, 1ull << 27) : mb;  // compact records: qid - q0 < 2^28
+    if (compactRecs) mb = std::min<uint64_t>(mb, 1ull << 27);  // compact records: qid - q0 < 2^28
+    return granularity > 1 ? std::max<uint64_t>(granularity, mb / granularity * granularity) : mb;
 }
 
 // a hit or task buffer's first size for batches of maxBatch patterns; a pass
@@ -130,9 +137,21 @@ inline uint32_t firstWorkCap(uint64_t maxBatch) {
 
 // batch boundaries: equal batches of <= maxBatch patterns, or (pipelined,
 // SAHARA_RAMP / SAHARA_RAMP_END: lists of pattern counts) given first and
-// last batches around equal middle ones
+// last batches around equal middle ones. granularity g > 1 (npat a multiple
+// of g, maxBatch one from maxBatchOf): the same plan made in groups of g
+// patterns, a ramp entry below g taken as one group and any other rounded
+// down to whole groups, so every boundary is a multiple of g, no batch is
+// empty and none exceeds maxBatch.
 inline std::vector<uint64_t> batchStarts(uint64_t npat, uint64_t maxBatch, std::vector<uint64_t> head,
-                                         std::vector<uint64_t> tail, bool serial) {
+                                         std::vector<uint64_t> tail, bool serial, uint64_t granularity = 1) {
+    if (granularity > 1) {
+        const uint64_t g = granularity;
+        for (auto* ramp : {&head, &tail})
+            for (auto& x : *ramp) x = std::max<uint64_t>(1, x / g);
+        std::vector<uint64_t> groups = batchStarts(npat / g, std::max<uint64_t>(1, maxBatch / g), head, tail, serial);
+        for (auto& x : groups) x *= g;
+        return groups;
+    }
     std::vector<uint64_t> bstart{0};
     uint64_t edges = 0;
     for (auto& x : head) edges += x = std::min(x, maxBatch);

@@ -104,19 +104,20 @@ constexpr uint32_t kQueueWords = 256;
 enum QueueAt : uint32_t { kQueueSeeds = 0, kQueueSeedTasks = kQueueWords, kQueueFmTasks = 2 * kQueueWords,
                          kQueuesWords = 3 * kQueueWords };
 // One batch's record in pinned host memory (Ctx::pinned), written by
-// kBatchTotals (words 0-11), kLocateFlagsOut (7), lociBatch and limitBatch (12-13, one after the other)
+// kBatchTotals (words 0-11), kLocateFlagsOut (7), lociBatch, pairsBatch and limitBatch (12-13, one after
+// the other) and pairsBatch (14-15)
 struct BatchRecord {
     uint32_t slot[7];      // the slot's counters, by SlotWord
     uint32_t locateFlags;  // the locate chain's flags word (kFlagLocate)
     uint64_t rows;         // the batch's row total
     uint32_t nbig, nhuge;  // long / huge segments
-    uint64_t kept;         // rows the loci stage keeps, then rows --max_hits keeps (each read before the next is written)
-    uint32_t pad[2];
+    uint64_t kept;         // rows the loci stage keeps, then the pair stage, then --max_hits (each read before the next is written)
+    uint64_t pairs;        // pairs that keep a hit (the pair stage; read after the batch's chain)
 };
 static_assert(sizeof(BatchRecord) == 64 && offsetof(BatchRecord, slot) == 0 &&
               offsetof(BatchRecord, locateFlags) == 4 * 7 && offsetof(BatchRecord, rows) == 4 * kSlotWords &&
               offsetof(BatchRecord, nbig) == 4 * 10 && offsetof(BatchRecord, nhuge) == 4 * 11 &&
-              offsetof(BatchRecord, kept) == 4 * 12, "BatchRecord is what kBatchTotals, lociBatch and limitBatch write");
+              offsetof(BatchRecord, kept) == 4 * 12, "BatchRecord is what kBatchTotals, lociBatch, pairsBatch and limitBatch write");
 
 // work counters of count mode (sahara_stats; Ctx::counters)
 constexpr uint32_t kCounters = 56;
@@ -285,5 +286,20 @@ struct LociBufs {
 // per-query segments rewritten for the records kept (what limitBatch reads next)
 uint64_t lociBatch(sahara_hit* out, uint64_t rows, uint32_t window, uint64_t* qoff, uint32_t nq, uint64_t qidBase,
                    LociBufs& B, DevBuf<sahara_hit>& buf, DevBuf<char>& tmp, uint64_t* hostKept, hipStream_t st);
+// qoff[q] = the first of the n sorted records whose qid is not below qidBase + q, for q in [0, nq] (loci.hip
+// kLociSegments): the per-query segments a stage that dropped records leaves for limitBatch
+void launchHitSegments(const sahara_hit* h, uint64_t n, uint64_t qidBase, uint32_t nq, uint64_t* qoff, hipStream_t st);
+
+// ---- pairs.hip: one batch's whole hits cut to those with a concordant mate (docs/semantics.md "Pairs")
+struct PairsBufs {
+    DevBuf<uint32_t> flag, num;         // per record: has a mate; the flags' inclusive sum
+    DevBuf<unsigned long long> pairs;   // one word: the pairs that keep a hit
+};
+// in place, kept records returned (host-synchronous, as lociBatch); *hostPairs (pinned) gets the pairs with a
+// kept hit once st has passed the call; qoff: the batch's per-query segments or nullptr, searched within if
+// `narrow`, written again for the records kept if `rewrite`
+uint64_t pairsBatch(sahara_hit* out, uint64_t rows, uint32_t len, uint32_t minFrag, uint32_t maxFrag, uint64_t* qoff,
+                    uint32_t nq, uint64_t qidBase, bool narrow, bool rewrite, PairsBufs& B, DevBuf<sahara_hit>& buf, DevBuf<char>& tmp,
+                    uint64_t* hostKept, uint64_t* hostPairs, hipStream_t st);
 
 }  // namespace sahara
