@@ -18,7 +18,7 @@ $(shell mkdir -p $(OBJDIR) && echo '#define SAHARA_BUILD_ID "$(BUILD_ID)"' > $(O
         (cmp -s $(OBJDIR)/build_id.h.new $(OBJDIR)/build_id.h || mv $(OBJDIR)/build_id.h.new $(OBJDIR)/build_id.h))
 
 # the library's translation units (csrc/NAME.hip or .cpp), listed once for the plain and the sanitizer build
-UNITS := index_build search_fm search_text locate_sort patterns hits loci pairs align capi capi_ctx capi_align capi_synth staging pass host_util scheme
+UNITS := index_build search_fm search_text locate_sort patterns hits loci pairs rescue align capi capi_ctx capi_align capi_synth staging pass host_util scheme
 OBJS  := $(UNITS:%=$(OBJDIR)/%.o)
 
 all: $(LIB) oracle $(if $(wildcard sahara_amd/cli/*.cpp),$(CLI),) tools/gather_bench

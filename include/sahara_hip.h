@@ -358,6 +358,37 @@ typedef struct sahara_pairs_stats {    /* 40 B */
 /* ... of the context's last search call; zeros if pairs were off. */
 int  sahara_gpu_pairs_stats(void* ctx, sahara_pairs_stats* stats);
 
+/* --- mate rescue (docs/semantics.md "Mate rescue") ---
+ * With pairs on, a hit whose partner query has no hit in its fragment window
+ * is dropped, even where the partner lies there with a few errors more than
+ * the search allows. With rescue on, such a hit (an anchor) gets its window
+ * scanned on the device for the partner's pattern with up to max_err errors
+ * (the e* of "Alignments", bound max_err, the call's edit flag); the best
+ * start of the window, if any, joins the hits as (qid ^ 3, seq_id, start, e*)
+ * before the pair stage runs, which then keeps both. The stage runs per batch
+ * after the loci stage and before the pair stage. max_anchors > 0: a query
+ * with more than that many anchors in a batch is left alone (it lies in a
+ * repeat); 0: no cap.
+ * on != 0: every later search call of this context rescues so; on == 0 (the
+ * default) restores the calls as they were. Refused with a negative code and
+ * a message: a NULL context, max_err outside [1, SAHARA_ALIGN_MAX_ERR], NULL
+ * stats. With rescue on a search call is refused before any device work if
+ * pairs are off, if max_fragment - max(min_fragment, len) reaches
+ * SAHARA_RESCUE_MAX_WINDOW (a policy: one anchor's scan is at most 64 rounds
+ * of a wave), or if len > 16383. */
+#define SAHARA_RESCUE_MAX_WINDOW 4096
+int  sahara_gpu_set_rescue(void* ctx, int on, uint32_t max_err, uint32_t max_anchors);
+typedef struct sahara_rescue_stats {   /* 48 B */
+    uint64_t anchors;         /* hits whose window was scanned */
+    uint64_t capped_queries;  /* queries left alone by max_anchors (counted per batch and index part) */
+    uint64_t starts;          /* window starts of those anchors */
+    uint64_t rescued;         /* distinct records added */
+    uint64_t batches;         /* batches the stage ran on */
+    double   kernel_ms;       /* device time of the stage (HIP events), summed over batches and index parts */
+} sahara_rescue_stats;
+/* ... of the context's last search call; zeros if rescue was off. */
+int  sahara_gpu_rescue_stats(void* ctx, sahara_rescue_stats* stats);
+
 /* Device-resident form of the same path for benchmarking: stage patterns and
  * scheme once, run search+locate+sort with results left in HBM, fetch later. */
 int  sahara_gpu_stage(void* ctx, const uint8_t* ranks, uint64_t n_patterns, uint32_t len,

@@ -106,6 +106,11 @@ class PairsStats(C.Structure):
                 ("kernel_ms", C.c_double)]
 
 
+class RescueStats(C.Structure):
+    _fields_ = [("anchors", C.c_uint64), ("capped_queries", C.c_uint64), ("starts", C.c_uint64),
+                ("rescued", C.c_uint64), ("batches", C.c_uint64), ("kernel_ms", C.c_double)]
+
+
 EXPORTED = {
     # name: (restype, argtypes)
     "sahara_gpu_last_error": (C.c_char_p, []),
@@ -125,6 +130,8 @@ EXPORTED = {
     "sahara_gpu_loci_stats": (C.c_int, [C.c_void_p, C.POINTER(LociStats)]),
     "sahara_gpu_set_pairs": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32]),
     "sahara_gpu_pairs_stats": (C.c_int, [C.c_void_p, C.POINTER(PairsStats)]),
+    "sahara_gpu_set_rescue": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32]),
+    "sahara_gpu_rescue_stats": (C.c_int, [C.c_void_p, C.POINTER(RescueStats)]),
     "sahara_gpu_select_part": (C.c_int, [C.c_void_p, C.c_uint32]),
     "sahara_gpu_part_info": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     "sahara_gpu_search": (C.c_int, [C.c_void_p, u8p, C.c_uint64, C.c_uint32, u32p, u32p, u32p,
@@ -378,6 +385,28 @@ class BiFMIndex:
         """Figures of the pair stage in the last search call (zeros if pairs were off)."""
         s = PairsStats()
         _check(lib().sahara_gpu_pairs_stats(self._h, C.byref(s)))
+        return {n: getattr(s, n) for n, _ in s._fields_}
+
+    def set_rescue(self, max_err, max_anchors=64):
+        """Mate rescue (docs/semantics.md "Mate rescue"), for calls with pairs
+        on: a hit whose partner has no hit in its fragment window gets that
+        window scanned for the partner's pattern with up to max_err errors
+        (1 to 8), and the best start found joins the hits before the pair
+        stage. A query with more than max_anchors such hits in a batch is left
+        alone (0: no cap). set_rescue(None) turns it off. The setting stays
+        until changed."""
+        if max_err is None:
+            _check(lib().sahara_gpu_set_rescue(self._h, 0, 0, 0))
+            return
+        k, a = int(max_err), int(max_anchors)
+        if not (0 <= k <= 0xFFFFFFFF and 0 <= a <= 0xFFFFFFFF):
+            raise ValueError("max_err and max_anchors must be in [0, 2^32)")
+        _check(lib().sahara_gpu_set_rescue(self._h, 1, k, a))
+
+    def rescue_stats(self):
+        """Figures of the mate rescue in the last search call (zeros if it was off)."""
+        s = RescueStats()
+        _check(lib().sahara_gpu_rescue_stats(self._h, C.byref(s)))
         return {n: getattr(s, n) for n, _ in s._fields_}
 
     # ---- device-resident path (bench) ----

@@ -449,9 +449,12 @@ int cmdSearch(int argc, char** argv) {
     // paired-end reads, the mates interleaved in the query file (docs/semantics.md "Pairs"): only hits with a
     // concordant mate are written
     Opt paired{{"--paired"}, true}, minFrag{{"--min-fragment"}, false, "0"}, maxFrag{{"--max-fragment"}, false, "500"};
+    // mate rescue (docs/semantics.md "Mate rescue"): a hit without a mate gets its fragment window scanned for the
+    // partner read with up to n errors; --rescue-anchors a: a read with more than a such hits is left alone (0: no cap)
+    Opt rescue{{"--rescue"}}, rescueAnchors{{"--rescue-anchors"}, false, "64"};
     Parser p;
     for (Opt* o : {&query, &index, &output, &gen, &dyn, &errors, &noRev, &mode, &dist, &maxHits, &limit, &gpus,
-                   &emitErr, &fmOnly, &emitCigar, &loci, &lociWindow, &paired, &minFrag, &maxFrag})
+                   &emitErr, &fmOnly, &emitCigar, &loci, &lociWindow, &paired, &minFrag, &maxFrag, &rescue, &rescueAnchors})
         p.add(*o);
     p.parse(argc, argv, 2);
     if (!p.positional.empty()) throw CliError("unexpected argument " + p.positional[0]);
@@ -479,6 +482,17 @@ int cmdSearch(int argc, char** argv) {
     }
     if (emitCigar.given && k > SAHARA_ALIGN_MAX_ERR)
         throw CliError("--emit-cigar aligns at most " + std::to_string(SAHARA_ALIGN_MAX_ERR) + " errors (-e)");
+    if (rescueAnchors.given && !rescue.given) throw CliError("--rescue-anchors needs --rescue");
+    const uint64_t rescueK = rescue.given ? toU64(rescue.value, "--rescue") : 0;
+    const uint64_t rescueA = toU64(rescueAnchors.value, "--rescue-anchors");
+    if (rescue.given) {
+        if (!paired.given) throw CliError("--rescue needs --paired (a mate is looked for in the fragment window)");
+        if (rescueK < 1 || rescueK > SAHARA_ALIGN_MAX_ERR)
+            throw CliError("--rescue takes 1 to " + std::to_string(SAHARA_ALIGN_MAX_ERR) + " errors");
+        if (rescueA > 0xFFFFFFFFull) throw CliError("--rescue-anchors is at most 4294967295");
+    }
+    // (a rescued hit carries up to --rescue errors: --emit-cigar aligns with the larger bound)
+    const uint32_t alignK = (uint32_t)std::max<uint64_t>((uint64_t)k, rescueK);
 
     // sigma dispatch (search.cpp:276-291)
     const uint64_t sigma = readSigma(index.value);
@@ -599,6 +613,8 @@ int cmdSearch(int argc, char** argv) {
         for (void* c : ctx) check(sahara_gpu_set_loci(c, 1, (uint32_t)lociW), "set loci");
     if (paired.given)  // every shard's context: shards split at whole pairs (shard.h)
         for (void* c : ctx) check(sahara_gpu_set_pairs(c, 1, (uint32_t)fragLo, (uint32_t)fragHi), "set pairs");
+    if (rescue.given)  // (a window lies on the anchor's record, and a pair in one shard)
+        for (void* c : ctx) check(sahara_gpu_set_rescue(c, 1, (uint32_t)rescueK, (uint32_t)rescueA), "set rescue");
     sahara_index_info info{};
     check(sahara_gpu_index_info(ctx[0], &info), "index info");
     timing.emplace_back("ld index", sw.reset());
@@ -692,6 +708,7 @@ int cmdSearch(int argc, char** argv) {
     std::vector<std::string> errs(ngpu);
     std::vector<sahara_loci_stats> devLoci(ngpu);
     std::vector<sahara_pairs_stats> devPairs(ngpu);
+    std::vector<sahara_rescue_stats> devRescue(ngpu);
     {
         std::vector<std::thread> th;
         for (uint32_t g = 0; g < ngpu; ++g) {
@@ -742,6 +759,7 @@ int cmdSearch(int argc, char** argv) {
                 devLocate[g] = (st.locate_ms + st.sort_ms) / 1e3;
                 if (lociOn) sahara_gpu_loci_stats(ctx[g], &devLoci[g]);
                 if (paired.given) sahara_gpu_pairs_stats(ctx[g], &devPairs[g]);
+                if (rescue.given) sahara_gpu_rescue_stats(ctx[g], &devRescue[g]);
                 devSearch[g] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
                 part.hits = hits;
                 part.n = nh;
@@ -756,12 +774,12 @@ int cmdSearch(int argc, char** argv) {
                         if (part.compact) {
                             rc = sahara_gpu_align_packed_compact(ctx[g], reads, (uint64_t)r0 * len, npos, ncount,
                                                                  r1 - r0, len, noRev.given ? 0 : 1, q1 - q0, alignEdit,
-                                                                 (uint32_t)k, &part.blocks, part.aln.data());
+                                                                 alignK, &part.blocks, part.aln.data());
                         } else {  // whole records (--max_hits, a multi-part index): the shard's patterns as ranks
                             const std::vector<uint8_t> pats =
                                 shardPatterns(reads, (uint64_t)r0 * len, npos, ncount, r1 - r0, len, !noRev.given,
                                               q1 - q0, (uint32_t)sigma);
-                            rc = sahara_gpu_align(ctx[g], pats.data(), q1 - q0, len, alignEdit, (uint32_t)k, hits, nh,
+                            rc = sahara_gpu_align(ctx[g], pats.data(), q1 - q0, len, alignEdit, alignK, hits, nh,
                                                   part.aln.data());
                         }
                         if (rc != 0) errs[g] = sahara_gpu_last_error();
@@ -816,6 +834,13 @@ int cmdSearch(int argc, char** argv) {
         for (const sahara_pairs_stats& s : devPairs) in += s.hits_in, kept += s.kept, np += s.pairs;
         std::printf("  pairs:               %llu of %llu hits, %llu pairs\n", kept, in, np);
     }
+    if (rescue.given) {
+        unsigned long long anchors = 0, starts = 0, found = 0, capped = 0;
+        for (const sahara_rescue_stats& s : devRescue)
+            anchors += s.anchors, starts += s.starts, found += s.rescued, capped += s.capped_queries;
+        std::printf("  rescue:              %llu mates from %llu anchors, %llu starts, %llu reads capped\n", found, anchors,
+                    starts, capped);
+    }
     // the index loads beside the query ingest: "ld index" above is the part of
     // its load the ingest did not hide; this is its whole load
     std::printf("  index load:          %10.2fs (beside ld queries)\n",
@@ -863,6 +888,9 @@ void help() {
         "                [--loci] [--loci-window <n>]   one hit per locus (window: -e's value, or n)\n"
         "                [--paired] [--min-fragment <n>] [--max-fragment <n>]   the query file holds mate pairs\n"
         "                interleaved; only hits with a concordant mate are written (fragment 0..500, or n)\n"
+        "                [--rescue <n>] [--rescue-anchors <a>]   with --paired: a hit without a mate gets its\n"
+        "                fragment window scanned for the other read with up to n errors (1..8); a read with\n"
+        "                more than a such hits is left alone (64; 0: no cap)\n"
         "  sahara read_simulator -o <fasta> [-i <reference>] [-l <len>] [-n <reads>] [-e <errors>]\n"
         "                [--substitution_errors n] [--insertion_errors n] [--deletion_errors n]\n"
         "                [--fasta_line_length n] [--seed s]\n"

@@ -12,41 +12,24 @@
 #include <algorithm>
 
 #include "align.h"
-#include "align_core.h"
+#include "align_device.h"
 #include "device_index.h"
 
 namespace sahara {
 
 namespace {
 
-constexpr uint32_t kAlignBlock = 64;  // one wave: the table of K = 8 is 19.1 KB of LDS per workgroup
+constexpr uint32_t kAlignBlock = kAlignLanes;  // one wave (align_device.h)
 
 static_assert(sizeof(sahara_alignment) == 24, "sahara_alignment is 24 B");
 static_assert(kAlignMaxErr == SAHARA_ALIGN_MAX_ERR && kAlignNone == SAHARA_ALIGN_NONE, "align_core.h mirrors the ABI");
 
-// (as search_text.hip bufferOf: loads past the end return 0 without a memory request)
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t alignBufferOf(const void* base, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, (int)bytes, 0x00020000);
-}
-
-struct TextBlocks {
-    __amdgpu_buffer_rsrc_t buf;
-    __device__ __forceinline__ Planes3 operator()(uint32_t b) const {
-        const auto v = __builtin_amdgcn_raw_buffer_load_b128(buf, b * 16u, 0, 0);
-        return {v[0], v[1], v[2]};
-    }
-};
 struct PatBlocks {
     const uint4* p;  // the lane's pattern
     __device__ __forceinline__ Planes3 operator()(uint32_t b) const {
         const uint4 v = p[b];
         return {v.x, v.y, v.z};
     }
-};
-struct LaneTable {  // entry k of this lane at lds[k * kAlignBlock + lane]
-    int16_t* t;
-    __device__ __forceinline__ int operator()(int k) const { return t[k * (int)kAlignBlock]; }
-    __device__ __forceinline__ void set(int k, int v) { t[k * (int)kAlignBlock] = (int16_t)v; }
 };
 
 template <bool COMPACT>
@@ -71,7 +54,7 @@ __global__ __launch_bounds__(kAlignBlock) void kAlignHits(AlignArgs a) {
         qid = h.qid;
         g = (uint32_t)(a.recStarts[h.seq_id - a.rec0] + h.pos);
     }
-    TextBlocks text{alignBufferOf(a.text3, a.text3Bytes)};
+    BufBlocks text{alignBufferOf(a.text3, a.text3Bytes)};
     PatBlocks pat{a.pats3 + qid * a.patBlocks};
     LaneTable L{alignLds + threadIdx.x};
     uint32_t err, refLen;
@@ -87,8 +70,7 @@ __global__ __launch_bounds__(kAlignBlock) void kAlignHits(AlignArgs a) {
 
 void launchAlignHits(const AlignArgs& a, hipStream_t st) {
     if (a.nHits == 0) return;
-    const uint32_t band = a.edit ? 2 * a.maxErr + 1 : 1;
-    const size_t lds = (size_t)(a.maxErr + 1) * band * kAlignBlock * sizeof(int16_t);
+    const size_t lds = alignTableBytes(a.maxErr, a.edit != 0);
     const uint64_t blocks = (a.nHits + kAlignBlock - 1) / kAlignBlock;
     if (blocks > 0x7FFFFFFFull) throw Error("alignment chunk too large");
     if (a.hits) hipLaunchKernelGGL(kAlignHits<false>, dim3((unsigned)blocks), dim3(kAlignBlock), lds, st, a);

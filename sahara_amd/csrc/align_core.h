@@ -44,18 +44,16 @@ SAHARA_HD Planes3 alignRead32(F& blocks, uint32_t at) {
     return {alignFunnel(hi.b0, lo.b0, sh), alignFunnel(hi.b1, lo.b1, sh), alignFunnel(hi.b2, lo.b2, sh)};
 }
 
-// One hit: pattern of m symbols (pat(b): its block b, b <= ceil(m / 32): the
-// block after the pattern is read and masked), text position g (text(b): text
-// block b, zero blocks after the text), bound K <= kAlignMaxErr. L holds
-// (K + 1) * (2 K + 1) entries. Result: err (kAlignNone: no alignment within
-// K), refLen, and the err edits, 16 bits each, in pattern order: edit s in
-// bits 16 (s % 4) of edLo (s < 4) or edHi.
+// The table build of one hit: pattern of m symbols (pat(b): its block b,
+// b <= ceil(m / 32): the block after the pattern is read and masked), text
+// position g (text(b): text block b, zero blocks after the text), bound
+// K <= kAlignMaxErr. L holds (K + 1) * (2 K + 1) entries; rows 0 .. e* of it
+// are filled. Returns e*, or -1 if no alignment costs K or less. For K below
+// the true e* the answer is -1, for any K at or above it the same e*: a cell
+// of cost e lies within |d| <= e and within m + e text symbols. (The mate
+// rescue's scan, rescue.hip, calls this alone, with a falling bound.)
 template <class PF, class TF, class LT>
-SAHARA_HD void alignOne(PF& pat, TF& text, uint32_t g, uint32_t m, uint32_t K, bool edit, LT& L, uint32_t& err,
-                        uint32_t& refLen, uint64_t& edLo, uint64_t& edHi) {
-    err = kAlignNone;
-    refLen = 0;
-    edLo = edHi = 0;
+SAHARA_HD int alignTable(PF& pat, TF& text, uint32_t g, uint32_t m, uint32_t K, bool edit, LT& L) {
     // the window: text symbols up to the first '$' (all planes 0: the pad after the text too)
     const uint32_t cap = edit ? m + K : m;
     uint32_t JM = 0;
@@ -109,7 +107,18 @@ SAHARA_HD void alignOne(PF& pat, TF& text, uint32_t g, uint32_t m, uint32_t K, b
             if (best == M) eStar = e;
         }
     }
-    if (eStar < 0) return;
+    return eStar;
+}
+
+// The backward walk over a table that alignTable built for the same m, K and
+// edit and that reached eStar >= 0: refLen and the edits, err = eStar (the
+// record stays NONE should the walk find no predecessor, which a table built
+// above never causes).
+template <class PF, class TF, class LT>
+SAHARA_HD void alignTrace(PF& pat, TF& text, uint32_t g, uint32_t m, uint32_t K, bool edit, LT& L, int eStar,
+                          uint32_t& err, uint32_t& refLen, uint64_t& edLo, uint64_t& edHi) {
+    const int B = edit ? (int)K : 0, W = 2 * B + 1;
+    const int M = (int)m;
     // ref_len: the end closest to m, ties to the smaller j
     int dEnd = 0;
     for (int t = 0; t <= B; ++t) {
@@ -173,6 +182,20 @@ SAHARA_HD void alignOne(PF& pat, TF& text, uint32_t g, uint32_t m, uint32_t K, b
     }
     err = (uint32_t)eStar;
     refLen = (uint32_t)(M + dEnd);
+}
+
+// One hit: the table, then the walk. Result: err (kAlignNone: no alignment
+// within K), refLen, and the err edits, 16 bits each, in pattern order: edit
+// s in bits 16 (s % 4) of edLo (s < 4) or edHi.
+template <class PF, class TF, class LT>
+SAHARA_HD void alignOne(PF& pat, TF& text, uint32_t g, uint32_t m, uint32_t K, bool edit, LT& L, uint32_t& err,
+                        uint32_t& refLen, uint64_t& edLo, uint64_t& edHi) {
+    err = kAlignNone;
+    refLen = 0;
+    edLo = edHi = 0;
+    const int eStar = alignTable(pat, text, g, m, K, edit, L);
+    if (eStar < 0) return;
+    alignTrace(pat, text, g, m, K, edit, L, eStar, err, refLen, edLo, edHi);
 }
 
 }  // namespace sahara

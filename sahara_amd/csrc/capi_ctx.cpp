@@ -125,7 +125,7 @@ Ctx* newCtx(int device) {
     for (Stream* s : {&c->st, &c->stB, &c->stC, &c->stD, &c->stE, &c->stF}) *s = Stream(hipStreamNonBlocking);
     for (Event* e : {&c->outCopied[0], &c->outCopied[1], &c->locStart, &c->locDone, &c->sortDone, &c->totalsDown,
                      &c->flagsDown, &c->recsMade, &c->lociStart, &c->lociDone,
-                     &c->pairsStart, &c->pairsDone})
+                     &c->pairsStart, &c->pairsDone, &c->rescueStart, &c->rescueDone})
         *e = Event(hipEventDefault);
     for (Event* e : {&c->totalsDownSleep, &c->flagsDownSleep}) *e = Event(hipEventDisableTiming | hipEventBlockingSync);
     for (auto& e : c->ringEv) e = Event(hipEventDisableTiming);
@@ -363,6 +363,24 @@ int sahara_gpu_pairs_stats(void* ctx, sahara_pairs_stats* stats) {
     return guarded([&] {
         if (!stats) throw Error("sahara_gpu_pairs_stats: null output");
         *stats = ctxOf(ctx)->pairs.stats;
+    });
+}
+
+int sahara_gpu_set_rescue(void* ctx, int on, uint32_t max_err, uint32_t max_anchors) {
+    return guarded([&] {
+        if (on && (max_err < 1 || max_err > SAHARA_ALIGN_MAX_ERR))
+            throw Error("sahara_gpu_set_rescue: max_err must be in [1, " + std::to_string(SAHARA_ALIGN_MAX_ERR) + "]");
+        Ctx* c = ctxOf(ctx);
+        c->rescue.on = on != 0;
+        c->rescue.maxErr = on ? max_err : 0u;
+        c->rescue.maxAnchors = on ? max_anchors : 0u;
+    });
+}
+
+int sahara_gpu_rescue_stats(void* ctx, sahara_rescue_stats* stats) {
+    return guarded([&] {
+        if (!stats) throw Error("sahara_gpu_rescue_stats: null output");
+        *stats = ctxOf(ctx)->rescue.stats;
     });
 }
 

@@ -347,6 +347,18 @@ struct Ctx {
         sahara_pairs_stats stats{};
         PairsBufs bufs;
     } pairs;
+    // The mate rescue (docs/semantics.md "Mate rescue"; rescue.hip): a setting
+    // of the context too (sahara_gpu_set_rescue), which needs the pair stage
+    // on: every batch gets the windows of its hits without a mate scanned for
+    // the partner's pattern within maxErr errors, after the loci stage and
+    // before the pair stage. stats: of the last search call, summed as the
+    // pairs' are.
+    struct Rescue {
+        bool on = false;
+        uint32_t maxErr = 0, maxAnchors = 0;
+        sahara_rescue_stats stats{};
+        RescueBufs bufs;
+    } rescue;
     // SAHARA_TIMING=2: host-side marks of one call (ms since its start, what)
     bool traceOn = false;
     std::chrono::steady_clock::time_point traceT0;
@@ -418,6 +430,7 @@ struct Ctx {
     Event locStart, locDone, sortDone, totalsDown, flagsDown, recsMade;
     Event lociStart, lociDone;  // around a batch's loci stage on stC (sahara_loci_stats.kernel_ms)
     Event pairsStart, pairsDone;  // around its pair stage (sahara_pairs_stats.kernel_ms)
+    Event rescueStart, rescueDone;  // around its mate rescue (sahara_rescue_stats.kernel_ms)
     // the finisher's waits in a streamed call, recorded in place of totalsDown
     // and beside flagsDown: blocking-sync events, so that it sleeps instead of
     // spinning a CPU that the packing threads need (a 16-CPU quota on the GPU box)

@@ -110,6 +110,15 @@ __global__ __launch_bounds__(256) void kPairGather(const sahara_hit* __restrict_
 
 }  // namespace
 
+// flag[i] = record i of the n sorted records has a concordant mate among them (kPairFlags): the pair
+// stage's first step, and the mate rescue's (rescue.hip), whose anchors are the records without one
+void launchPairFlags(const sahara_hit* h, uint64_t n, uint64_t dmin, uint64_t dmax, const uint64_t* qoff,
+                     uint64_t qidBase, uint32_t nq, uint32_t* flag, hipStream_t st) {
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>((n + 255) / 256, 8192);
+    hipLaunchKernelGGL(kPairFlags, dim3(blocks), dim3(256), 0, st, h, n, dmin, dmax, qoff, qidBase, nq, flag);
+    SH_HIP(hipGetLastError());
+}
+
 // One batch's whole hits (out, rows; canonical order, a pair's four qids all
 // in the batch) reduced in place to the hits with a concordant mate for
 // pattern length len and fragments in [minFrag, maxFrag] (maxFrag >= len: the
@@ -136,9 +145,7 @@ uint64_t pairsBatch(sahara_hit* out, uint64_t rows, uint32_t len, uint32_t minFr
     B.pairs.reserve(1);
     const PairDist d = pairDist(len, minFrag, maxFrag);
     const uint32_t blocks = (uint32_t)std::min<uint64_t>((rows + 255) / 256, 8192);
-    hipLaunchKernelGGL(kPairFlags, dim3(blocks), dim3(256), 0, st, out, rows, d.dmin, d.dmax,
-                       narrow ? (const uint64_t*)qoff : nullptr, qidBase, nq, B.flag.ptr);
-    SH_HIP(hipGetLastError());
+    launchPairFlags(out, rows, d.dmin, d.dmax, narrow ? (const uint64_t*)qoff : nullptr, qidBase, nq, B.flag.ptr, st);
     size_t bytes = 0;
     SH_HIP(rocprim::inclusive_scan(nullptr, bytes, B.flag.ptr, B.num.ptr, (size_t)rows, rocprim::plus<uint32_t>(), st));
     tmp.reserve(bytes + 256);

@@ -10,6 +10,8 @@
 #include <sys/prctl.h>
 
 #include "ctx.h"
+#include "align_core.h"
+#include "rescue_core.h"
 
 namespace sahara {
 
@@ -34,7 +36,22 @@ DeviceIndex& partOf(Ctx* c, uint32_t p) { return p == 0 ? c->I : c->more.at(p - 
 // among the merged hits iff it has one among its own part's: the union of the
 // parts' kept hits is the kept hits of the merged call. (A pair may keep hits
 // in several parts: the stats' pairs then count it once per part.)
+// The mate rescue on a multi-part index: per part as well. A window lies on
+// the anchor's record and a record lies wholly in one part, whose text and
+// record starts the scan reads; an anchor of the merged hits is an anchor of
+// its part's hits, since its mates could only lie on its own record.
 void checkPairsCall(const Ctx* c, uint64_t npat, uint32_t len) {
+    if (c->rescue.on) {  // (docs/semantics.md "Mate rescue", refused calls)
+        if (!c->pairs.on) throw Error("rescue: needs pairs on (a mate is looked for in the pair rule's fragment window)");
+        if (len > kAlignMaxLen)
+            throw Error("rescue: the pattern length " + std::to_string(len) + " is above " + std::to_string(kAlignMaxLen));
+        if (c->pairs.maxFrag >= len) {
+            const PairDist d = pairDist(len, c->pairs.minFrag, c->pairs.maxFrag);
+            if (d.dmax - d.dmin >= kRescueMaxWindow)
+                throw Error("rescue: the fragment window of " + std::to_string(d.dmax - d.dmin + 1) +
+                            " starts is above SAHARA_RESCUE_MAX_WINDOW (" + std::to_string(kRescueMaxWindow) + ")");
+        }
+    }
     if (!c->pairs.on) return;
     if (c->pairs.maxFrag < len)
         throw Error("pairs: max_fragment " + std::to_string(c->pairs.maxFrag) + " is below the pattern length " +
@@ -47,6 +64,7 @@ void checkPairsCall(const Ctx* c, uint64_t npat, uint32_t len) {
 void run(Ctx* c, bool count) {
     c->loci.stats = sahara_loci_stats{};  // of this call: the passes below add to them
     c->pairs.stats = sahara_pairs_stats{};
+    c->rescue.stats = sahara_rescue_stats{};
     if (c->sk.staged) checkPairsCall(c, c->npat, c->m);
     if (c->more.empty()) return runOne(c, count);
     // (rounds mask a query by its rows in one part; "found" is decided across the parts: capi.cpp bestOnHost)
@@ -110,11 +128,13 @@ void runOne(Ctx* c, bool count) {
     bool overflow = false;
     const sahara_loci_stats lociBefore = c->loci.stats;  // (a multi-part call's earlier parts)
     const sahara_pairs_stats pairsBefore = c->pairs.stats;
+    const sahara_rescue_stats rescueBefore = c->rescue.stats;
     runPass(c, count, false, S, overflow);
     if (overflow) {
         S = sahara_stats{};
         c->loci.stats = lociBefore;  // the batches finished before the overflow are redone
         c->pairs.stats = pairsBefore;
+        c->rescue.stats = rescueBefore;
         runPass(c, count, true, S, overflow);
     }
     S.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -397,6 +417,7 @@ struct Pass {
     uint32_t seenTask = 0, seenHit = 0;  // pipelined overflow: the caps the re-run needs
     bool lociRan = false;                // the batch just finished ran the loci stage (finishCheck reads its span)
     bool pairsRan = false;               // ... the pair stage (its span and its pairs count)
+    bool rescueRan = false;              // ... the mate rescue (its span)
 
     Ctx::Slot& slotOf(uint64_t b) const { return c->slot[b % Ctx::kSlots]; }
 
@@ -677,12 +698,46 @@ struct Pass {
             ++L.batches;
             SH_HIP(hipEventRecord(c->lociStart, sC));
             // (the segments rewritten for whichever stage reads them next)
-            const bool segments = c->sk.limitN || (c->pairs.on && P.k.pairsNarrow);
+            const bool segments = c->sk.limitN || (c->pairs.on && P.k.pairsNarrow) || c->rescue.on;
             rows = lociBatch(c->out.ptr + c->nout, rows, c->loci.window, segments ? c->qoff.ptr : nullptr,
                              (uint32_t)nb, q0, c->loci.bufs, c->limitBuf, c->tmp, &rec.kept, sC);
             SH_HIP(hipEventRecord(c->lociDone, sC));
             L.loci += rows;
             d = decide(rows);  // (never direct, as below)
+        }
+        // Mate rescue (docs/semantics.md "Mate rescue"): the hits without a mate
+        // get their fragment windows scanned for the partner's pattern, and
+        // what that finds joins the batch's hits before the pair stage cuts
+        // them. The batch may grow here, by no more than it has anchors: c->out
+        // grows between the stage's halves, once the count is known, and keeps
+        // the batch's records.
+        rescueRan = c->rescue.on && c->pairs.on && rows != 0;
+        if (rescueRan) {
+            sahara_rescue_stats& R = c->rescue.stats;
+            ++R.batches;
+            SH_HIP(hipEventRecord(c->rescueStart, sC));
+            const RescueIn in{c->m, c->pairs.minFrag, c->pairs.maxFrag, c->rescue.maxErr, c->rescue.maxAnchors, c->edit,
+                              c->I.dRecStarts.ptr, (uint32_t)c->I.recStarts.size(), c->I.n, c->I.text3.ptr,
+                              c->pats3.ptr + q0 * c->patBlocks, c->patBlocks, c->qoff.ptr, (uint32_t)nb, q0,
+                              P.k.pairsNarrow};
+            RescueCounts n{};
+            rescueFind(c->out.ptr + c->nout, rows, in, c->rescue.bufs, c->tmp, n, sC);
+            if (const uint64_t need = c->nout + rows + n.rescued; need > c->out.cap) {
+                SH_HIP(hipStreamSynchronize(c->stF));  // sink copies may still read the old buffer
+                c->out.growKeeping(std::max<size_t>(need + need / 2, 1024), c->nout + rows, sC);
+            }
+            rows = rescueMerge(c->out.ptr + c->nout, rows, n.rescued, in, c->rescue.bufs, c->limitBuf, c->tmp, sC);
+            SH_HIP(hipEventRecord(c->rescueDone, sC));
+            R.anchors += n.anchors;
+            R.capped_queries += n.cappedQueries;
+            R.starts += n.starts;
+            R.rescued += n.rescued;
+            d = decide(rows);
+            if (d.needRecs && c->nout + rows > c->outRecs.cap) {  // (sized for the sorted rows above)
+                SH_HIP(hipStreamSynchronize(c->stF));
+                const uint64_t need = c->nout + rows;
+                c->outRecs.growKeeping(std::max<size_t>(need + need / 2, 1024), std::min<size_t>(c->nout, c->outRecs.cap), sC);
+            }
         }
         // Pairs (docs/semantics.md "Pairs"): of what is left, the hits with a
         // concordant mate in the batch, which holds whole pairs (makePlan).
@@ -779,6 +834,10 @@ struct Pass {
         if (lociRan) {
             SH_HIP(hipEventElapsedTime(&ms, c->lociStart, c->lociDone));
             c->loci.stats.kernel_ms += ms;
+        }
+        if (rescueRan) {
+            SH_HIP(hipEventElapsedTime(&ms, c->rescueStart, c->rescueDone));
+            c->rescue.stats.kernel_ms += ms;
         }
         if (pairsRan) {  // (flagsDown has passed the stage's last copy, the one into the batch's record)
             SH_HIP(hipEventElapsedTime(&ms, c->pairsStart, c->pairsDone));

@@ -301,5 +301,45 @@ struct PairsBufs {
 uint64_t pairsBatch(sahara_hit* out, uint64_t rows, uint32_t len, uint32_t minFrag, uint32_t maxFrag, uint64_t* qoff,
                     uint32_t nq, uint64_t qidBase, bool narrow, bool rewrite, PairsBufs& B, DevBuf<sahara_hit>& buf, DevBuf<char>& tmp,
                     uint64_t* hostKept, uint64_t* hostPairs, hipStream_t st);
+// flag[i] = record i of the n sorted records has a concordant mate among them (qoff: searched within the
+// partner's segment, or nullptr)
+void launchPairFlags(const sahara_hit* h, uint64_t n, uint64_t dmin, uint64_t dmax, const uint64_t* qoff,
+                     uint64_t qidBase, uint32_t nq, uint32_t* flag, hipStream_t st);
+
+// ---- rescue.hip: the mates that did not map, looked for beside the hits without one (docs/semantics.md
+// "Mate rescue")
+struct RescueBufs {
+    DevBuf<uint32_t> flag, num, anchors;     // per record: has a mate, then is an anchor; the anchor flags'
+                                             // inclusive sum (the cap); the anchors' indices
+    DevBuf<sahara_hit> found, sorted;        // per anchor: its rescued record or a sentinel; sorted, then distinct
+    DevBuf<unsigned long long> words;        // kRescueWords counters
+    PinnedBuf<unsigned long long> host;      // ... as the host reads them
+};
+struct RescueIn {
+    uint32_t len, minFrag, maxFrag;          // the pair rule's window (pairs_core.h pairDist)
+    uint32_t maxErr, maxAnchors;             // K; A (0: no cap)
+    bool edit;
+    const uint64_t* recStarts;               // the part's records and text
+    uint32_t nrec;
+    uint64_t textLen;
+    const uint4* text3;
+    const uint4* pats3;                      // the batch's patterns (qid qidBase first), patBlocks blocks each
+    uint32_t patBlocks;
+    uint64_t* qoff;                          // the batch's per-query segments (nq + 1 offsets), rewritten where records join
+    uint32_t nq;
+    uint64_t qidBase;
+    bool narrow;                             // kPairFlags searches within the partner's segment
+};
+struct RescueCounts {
+    uint64_t anchors, cappedQueries, starts, rescued;
+};
+// The stage in two host-synchronous halves, so that the caller can grow the batch's buffer between them:
+// rescueFind scans the anchors of the batch's whole hits (h, rows; canonical order) and leaves the distinct
+// rescued records in B.found (counts.rescued of them); rescueMerge merges those r records into h, which has
+// room for rows + r, rewrites the per-query segments and returns the records there are then.
+void rescueFind(const sahara_hit* h, uint64_t rows, const RescueIn& in, RescueBufs& B, DevBuf<char>& tmp,
+                RescueCounts& counts, hipStream_t st);
+uint64_t rescueMerge(sahara_hit* h, uint64_t rows, uint64_t r, const RescueIn& in, RescueBufs& B, DevBuf<sahara_hit>& buf,
+                     DevBuf<char>& tmp, hipStream_t st);
 
 }  // namespace sahara
