@@ -579,10 +579,10 @@ static void bestOnHost(Ctx* c, const uint8_t* ranks, uint64_t n_patterns, uint32
         acc.total_ms += c->stats.total_ms;
         acc.hits += c->stats.hits;
         acc.patterns += c->stats.patterns;
-        lociAcc.hits_in += c->loci.stats.hits_in;
-        lociAcc.loci += c->loci.stats.loci;
-        lociAcc.batches += c->loci.stats.batches;
-        lociAcc.kernel_ms += c->loci.stats.kernel_ms;
+        lociAcc.hits_in += c->stageStats.loci.hits_in;
+        lociAcc.loci += c->stageStats.loci.loci;
+        lociAcc.batches += c->stageStats.loci.batches;
+        lociAcc.kernel_ms += c->stageStats.loci.kernel_ms;
         std::vector<char> found(todo.size(), 0);
         for (auto& h : v) {
             found[h.qid] = 1;
@@ -595,7 +595,7 @@ static void bestOnHost(Ctx* c, const uint8_t* ranks, uint64_t n_patterns, uint32
         todo.resize(w);
     }
     c->stats = acc;
-    c->loci.stats = lociAcc;
+    c->stageStats.loci = lociAcc;
     std::sort(all.begin(), all.end(), hitLess);
     if (max_hits) limitHits(all, max_hits);
     handOver(all, hits, n_hits);

@@ -124,9 +124,10 @@ Ctx* newCtx(int device) {
     // memory-bound kernels on the other streams ran 1.4-1.8x longer, r5.)
     for (Stream* s : {&c->st, &c->stB, &c->stC, &c->stD, &c->stE, &c->stF}) *s = Stream(hipStreamNonBlocking);
     for (Event* e : {&c->outCopied[0], &c->outCopied[1], &c->locStart, &c->locDone, &c->sortDone, &c->totalsDown,
-                     &c->flagsDown, &c->recsMade, &c->lociStart, &c->lociDone,
-                     &c->pairsStart, &c->pairsDone, &c->rescueStart, &c->rescueDone})
+                     &c->flagsDown, &c->recsMade})
         *e = Event(hipEventDefault);
+    for (Event* stage : {c->stageStart, c->stageDone})
+        for (uint32_t s = 0; s < kStages; ++s) stage[s] = Event(hipEventDefault);
     for (Event* e : {&c->totalsDownSleep, &c->flagsDownSleep}) *e = Event(hipEventDisableTiming | hipEventBlockingSync);
     for (auto& e : c->ringEv) e = Event(hipEventDisableTiming);
     // the streamed upload's pinned ring, pinned while the caller builds or
@@ -345,7 +346,7 @@ int sahara_gpu_set_loci(void* ctx, int on, uint32_t window) {
 int sahara_gpu_loci_stats(void* ctx, sahara_loci_stats* stats) {
     return guarded([&] {
         if (!stats) throw Error("sahara_gpu_loci_stats: null output");
-        *stats = ctxOf(ctx)->loci.stats;
+        *stats = ctxOf(ctx)->stageStats.loci;
     });
 }
 
@@ -362,7 +363,7 @@ int sahara_gpu_set_pairs(void* ctx, int on, uint32_t min_fragment, uint32_t max_
 int sahara_gpu_pairs_stats(void* ctx, sahara_pairs_stats* stats) {
     return guarded([&] {
         if (!stats) throw Error("sahara_gpu_pairs_stats: null output");
-        *stats = ctxOf(ctx)->pairs.stats;
+        *stats = ctxOf(ctx)->stageStats.pairs;
     });
 }
 
@@ -380,7 +381,7 @@ int sahara_gpu_set_rescue(void* ctx, int on, uint32_t max_err, uint32_t max_anch
 int sahara_gpu_rescue_stats(void* ctx, sahara_rescue_stats* stats) {
     return guarded([&] {
         if (!stats) throw Error("sahara_gpu_rescue_stats: null output");
-        *stats = ctxOf(ctx)->rescue.stats;
+        *stats = ctxOf(ctx)->stageStats.rescue;
     });
 }
 

@@ -322,41 +322,56 @@ struct Ctx {
         outRecs.reserve(n);
     }
     std::vector<uint64_t> recStartsEnd;   // record starts + the text length (sahara_hit_blocks.rec_starts)
-    DevBuf<uint32_t> limitCnt;            // limitBatch's buffers (sk.limitN)
-    DevBuf<uint64_t> limitOff;
-    DevBuf<sahara_hit> limitBuf;
+    // The stages a batch's sorted whole hits go through before they leave the
+    // device (pass_plan.h Stage; pass.cpp Pass::stages). stageScratch: where
+    // each gathers the records it leaves (search.h BatchView::scratch).
+    DevBuf<sahara_hit> stageScratch;
+    LimitBufs limit;                      // --max_hits (sk.limitN; hits.hip limitBatch)
+    // The stages' figures of the last search call, summed over its batches,
+    // parts and host besthits passes; together, so that a call clears them
+    // and an overflow re-run restores them as one value (pass.cpp run, runOne).
+    struct StageStats {
+        sahara_loci_stats loci{};
+        sahara_rescue_stats rescue{};
+        sahara_pairs_stats pairs{};
+        // by Stage, what every stage keeps alike: the batches it ran on and its
+        // HIP-event time (--max_hits keeps no figures: nulls)
+        struct Figures {
+            uint64_t* batches;
+            double* kernelMs;
+        };
+        Figures figures(uint32_t stage) {
+            const Figures f[kStages] = {{&loci.batches, &loci.kernel_ms}, {&rescue.batches, &rescue.kernel_ms},
+                                        {&pairs.batches, &pairs.kernel_ms}, {nullptr, nullptr}};
+            return f[stage];
+        }
+    } stageStats;
     // The loci stage (docs/semantics.md "Loci"; loci.hip): a setting of the
     // context, not of a call (sahara_gpu_set_loci): when on, every batch of
     // every pass cuts its whole hits to one record per locus right after the
-    // sort (pass.cpp finish). stats: of the last search call, summed over its
-    // batches, parts and host besthits passes.
+    // sort.
     struct Loci {
         bool on = false;
         uint32_t window = 0;
-        sahara_loci_stats stats{};
         LociBufs bufs;
     } loci;
     // The pair stage (docs/semantics.md "Pairs"; pairs.hip): a setting of the
     // context as well (sahara_gpu_set_pairs): when on, every batch of every
     // pass, cut at multiples of four patterns, keeps only its hits with a
-    // concordant mate, after the loci stage and before --max_hits. stats: of
-    // the last search call, summed as the loci's are.
+    // concordant mate, after the loci stage and before --max_hits.
     struct Pairs {
         bool on = false;
         uint32_t minFrag = 0, maxFrag = 0;
-        sahara_pairs_stats stats{};
         PairsBufs bufs;
     } pairs;
     // The mate rescue (docs/semantics.md "Mate rescue"; rescue.hip): a setting
     // of the context too (sahara_gpu_set_rescue), which needs the pair stage
     // on: every batch gets the windows of its hits without a mate scanned for
     // the partner's pattern within maxErr errors, after the loci stage and
-    // before the pair stage. stats: of the last search call, summed as the
-    // pairs' are.
+    // before the pair stage.
     struct Rescue {
         bool on = false;
         uint32_t maxErr = 0, maxAnchors = 0;
-        sahara_rescue_stats stats{};
         RescueBufs bufs;
     } rescue;
     // SAHARA_TIMING=2: host-side marks of one call (ms since its start, what)
@@ -428,9 +443,9 @@ struct Ctx {
     // sort + decode done (timing), the batch's totals and its locate flags
     // in the pinned record, its compact records made
     Event locStart, locDone, sortDone, totalsDown, flagsDown, recsMade;
-    Event lociStart, lociDone;  // around a batch's loci stage on stC (sahara_loci_stats.kernel_ms)
-    Event pairsStart, pairsDone;  // around its pair stage (sahara_pairs_stats.kernel_ms)
-    Event rescueStart, rescueDone;  // around its mate rescue (sahara_rescue_stats.kernel_ms)
+    // around each of a batch's stages on stC, by Stage (their stats' kernel_ms;
+    // --max_hits keeps no figures and records none)
+    Event stageStart[kStages], stageDone[kStages];
     // the finisher's waits in a streamed call, recorded in place of totalsDown
     // and beside flagsDown: blocking-sync events, so that it sleeps instead of
     // spinning a CPU that the packing threads need (a 16-CPU quota on the GPU box)

@@ -91,6 +91,24 @@ struct DevBuf {  // minimal owning device buffer that only ever grows
     }
 };
 
+// room for n elements in a buffer that follows a batch's row count: grown with
+// 25 % + 1024 to spare, so that batches a little larger do not allocate again
+template <typename T>
+void room(DevBuf<T>& b, uint64_t n) {
+    if (b.cap < n) b.reserve(n + n / 4 + 1024);
+}
+
+// rocPRIM's two calls: call(nullptr, bytes) says how much temporary storage
+// the primitive wants, `tmp` grows to that, call(tmp.ptr, bytes) runs it.
+// call: (void* temp, size_t& bytes) -> hipError_t.
+template <typename F>
+void withTemp(DevBuf<char>& tmp, F&& call) {
+    size_t bytes = 0;
+    SH_HIP(call(nullptr, bytes));
+    tmp.reserve(bytes + 256);
+    SH_HIP(call(tmp.ptr, bytes));
+}
+
 // Owners of the other HIP handles: move-only, empty when default-constructed,
 // released on destruction (an error there is ignored). Stream and Event stand
 // wherever HIP takes the raw handle.

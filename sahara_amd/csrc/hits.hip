@@ -1,6 +1,7 @@
 // hits.hip — what happens to a batch's hit records after the sort: digest,
 // copies with shifted ids, the multi-part merge by query, --max_hits on the
-// device, and the compact 8-B download records and their way back (gfx950).
+// device with what the batch's stages share (replaceBatch, scanFlagsCount),
+// and the compact 8-B download records and their way back (gfx950).
 
 #include <hip/hip_runtime.h>
 
@@ -135,34 +136,67 @@ __global__ void kLimitWrite(const sahara_hit* __restrict__ h, const uint64_t* __
     }
 }
 
-// Applies --max_hits n to one batch's hits (out, rows; per-query segments
-// qoff[0..nq]) in place; returns the rows kept. Host-synchronous (the kept
-// total sizes the rest of the batch's chain): read back through hostKept,
-// 8 B of pinned memory.
-uint64_t limitBatch(sahara_hit* out, uint64_t rows, const uint64_t* qoff, uint32_t nq, uint32_t n,
-                    DevBuf<uint32_t>& kcnt, DevBuf<uint64_t>& koff, DevBuf<sahara_hit>& buf, DevBuf<char>& tmp,
-                    uint64_t* hostKept, hipStream_t st) {
-    if (rows == 0 || nq == 0) return rows;
-    kcnt.reserve((size_t)nq + 1);
-    koff.reserve((size_t)nq + 1);
+// Applies --max_hits n to the batch in place, the last of its stages
+// (search.h BatchView). Host-synchronous: the kept total comes back through
+// v.kept.
+void limitBatch(BatchView& v, uint32_t n, LimitBufs& B) {
+    if (v.rows == 0 || v.nq == 0) return;
+    const uint32_t nq = v.nq;
+    B.cnt.reserve((size_t)nq + 1);
+    B.off.reserve((size_t)nq + 1);
     const uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>((nq + 256) / 256, 16384));
-    hipLaunchKernelGGL(kLimitCount, dim3(blocks), dim3(256), 0, st, out, qoff, nq, n, kcnt.ptr);
+    hipLaunchKernelGGL(kLimitCount, dim3(blocks), dim3(256), 0, v.st, v.hits, v.qoff, nq, n, B.cnt.ptr);
     SH_HIP(hipGetLastError());
-    size_t bytes = 0;
-    SH_HIP(rocprim::exclusive_scan(nullptr, bytes, kcnt.ptr, koff.ptr, (uint64_t)0, (size_t)nq + 1,
-                                   rocprim::plus<uint64_t>(), st));
-    tmp.reserve(bytes + 256);
-    SH_HIP(rocprim::exclusive_scan(tmp.ptr, bytes, kcnt.ptr, koff.ptr, (uint64_t)0, (size_t)nq + 1,
-                                   rocprim::plus<uint64_t>(), st));
-    SH_HIP(hipMemcpyAsync(hostKept, koff.ptr + nq, 8, hipMemcpyDeviceToHost, st));
-    SH_HIP(hipStreamSynchronize(st));
-    const uint64_t kept = *hostKept;
-    if (kept == rows) return rows;  // nothing to drop in this batch
-    buf.reserve(std::max<uint64_t>(kept, 1));
-    hipLaunchKernelGGL(kLimitWrite, dim3(blocks), dim3(256), 0, st, out, qoff, nq, n, koff.ptr, buf.ptr);
+    withTemp(v.tmp, [&](void* temp, size_t& bytes) {
+        return rocprim::exclusive_scan(temp, bytes, B.cnt.ptr, B.off.ptr, (uint64_t)0, (size_t)nq + 1,
+                                       rocprim::plus<uint64_t>(), v.st);
+    });
+    SH_HIP(hipMemcpyAsync(v.kept, B.off.ptr + nq, 8, hipMemcpyDeviceToHost, v.st));
+    SH_HIP(hipStreamSynchronize(v.st));
+    const uint64_t kept = *v.kept;
+    if (kept == v.rows) return;  // nothing to drop in this batch
+    v.scratch.reserve(std::max<uint64_t>(kept, 1));
+    hipLaunchKernelGGL(kLimitWrite, dim3(blocks), dim3(256), 0, v.st, v.hits, v.qoff, nq, n, B.off.ptr, v.scratch.ptr);
     SH_HIP(hipGetLastError());
-    if (kept) SH_HIP(hipMemcpyAsync(out, buf.ptr, kept * sizeof(sahara_hit), hipMemcpyDeviceToDevice, st));
-    return kept;
+    replaceBatch(v, kept);
+}
+
+namespace {
+
+// The per-query segments of n sorted records: qoff[q] = the first of them
+// whose qid is not below qidBase + q, qoff[nq] = n. One binary search per query.
+__global__ void kLociSegments(const sahara_hit* __restrict__ h, uint64_t loci, uint64_t qidBase, uint32_t nq,
+                              uint64_t* __restrict__ qoff) {
+    for (uint32_t q = blockIdx.x * blockDim.x + threadIdx.x; q <= nq; q += gridDim.x * blockDim.x) {
+        uint64_t lo = 0, hi = loci;
+        while (lo < hi) {
+            const uint64_t mid = lo + (hi - lo) / 2;
+            if (h[mid].qid < qidBase + q) lo = mid + 1;
+            else hi = mid;
+        }
+        qoff[q] = lo;
+    }
+}
+
+}  // namespace
+
+void replaceBatch(BatchView& v, uint64_t n) {
+    if (n) SH_HIP(hipMemcpyAsync(v.hits, v.scratch.ptr, n * sizeof(sahara_hit), hipMemcpyDeviceToDevice, v.st));
+    v.rows = n;
+    if (!v.later) return;
+    const uint32_t qblocks = std::min<uint32_t>(v.nq / 256 + 1, 16384);
+    hipLaunchKernelGGL(kLociSegments, dim3(qblocks), dim3(256), 0, v.st, v.hits, n, v.q0, v.nq, v.qoff);
+    SH_HIP(hipGetLastError());
+}
+
+uint64_t scanFlagsCount(uint32_t* flag, uint32_t* num, BatchView& v) {
+    withTemp(v.tmp, [&](void* temp, size_t& bytes) {
+        return rocprim::inclusive_scan(temp, bytes, flag, num, (size_t)v.rows, rocprim::plus<uint32_t>(), v.st);
+    });
+    *v.kept = 0;  // (the count is 32 bits: the low half of the word)
+    SH_HIP(hipMemcpyAsync(v.kept, num + (v.rows - 1), 4, hipMemcpyDeviceToHost, v.st));
+    SH_HIP(hipStreamSynchronize(v.st));
+    return *v.kept;
 }
 
 // Stable sort of hit records by qid (rocPRIM's LSD radix sort is stable):
@@ -183,10 +217,9 @@ void sortHitsByQid(const sahara_hit* in, uint64_t n, uint64_t nqid, sahara_hit* 
     const uint64_t blocks = std::min<uint64_t>((n + 255) / 256, 8192);
     hipLaunchKernelGGL(kQidKeys, dim3((unsigned)blocks), dim3(256), 0, st, in, n, B.k0.ptr, B.v0.ptr);
     SH_HIP(hipGetLastError());
-    size_t bytes = 0;
-    SH_HIP(rocprim::radix_sort_pairs(nullptr, bytes, B.k0.ptr, B.k1.ptr, B.v0.ptr, B.v1.ptr, (size_t)n, 0, endBit, st));
-    tmp.reserve(bytes + 256);
-    SH_HIP(rocprim::radix_sort_pairs(tmp.ptr, bytes, B.k0.ptr, B.k1.ptr, B.v0.ptr, B.v1.ptr, (size_t)n, 0, endBit, st));
+    withTemp(tmp, [&](void* temp, size_t& bytes) {
+        return rocprim::radix_sort_pairs(temp, bytes, B.k0.ptr, B.k1.ptr, B.v0.ptr, B.v1.ptr, (size_t)n, 0, endBit, st);
+    });
     hipLaunchKernelGGL(kGatherHits, dim3((unsigned)blocks), dim3(256), 0, st, in, B.v1.ptr, n, out);
     SH_HIP(hipGetLastError());
     SH_HIP(hipStreamSynchronize(st));

@@ -340,13 +340,12 @@ void suffixArray(const uint8_t* dT, uint64_t N, uint32_t* dSA, hipStream_t st) {
     SH_HIP(hipGetLastError());
     rocprim::double_buffer<uint64_t> kb(k0.ptr, k1.ptr);
     rocprim::double_buffer<uint32_t> vb(dSA, v1.ptr);
-    size_t tmpBytes = 0;
-    SH_HIP(rocprim::radix_sort_pairs(nullptr, tmpBytes, kb, vb, (size_t)N, 0, 64, st));
-    size_t scanBytes = 0;
-    SH_HIP(rocprim::inclusive_scan(nullptr, scanBytes, g.ptr, g.ptr, (size_t)N, rocprim::maximum<uint32_t>(), st));
-    tmp.reserve(std::max(tmpBytes, scanBytes) + 256);
-    size_t tb = tmp.cap;
-    SH_HIP(rocprim::radix_sort_pairs(tmp.ptr, tb, kb, vb, (size_t)N, 0, 63, st));
+    auto sortPairs = [&](unsigned endBit) {
+        withTemp(tmp, [&](void* temp, size_t& bytes) {
+            return rocprim::radix_sort_pairs(temp, bytes, kb, vb, (size_t)N, 0, endBit, st);
+        });
+    };
+    sortPairs(63);
 
     uint64_t h = 21;
     for (int round = 0;; ++round) {
@@ -358,13 +357,13 @@ void suffixArray(const uint8_t* dT, uint64_t N, uint32_t* dSA, hipStream_t st) {
         SH_HIP(hipStreamSynchronize(st));
         if (heads == N) break;
         if (round > 40) throw Error("suffix array construction did not converge");
-        tb = tmp.cap;
-        SH_HIP(rocprim::inclusive_scan(tmp.ptr, tb, g.ptr, g.ptr, (size_t)N, rocprim::maximum<uint32_t>(), st));
+        withTemp(tmp, [&](void* temp, size_t& bytes) {
+            return rocprim::inclusive_scan(temp, bytes, g.ptr, g.ptr, (size_t)N, rocprim::maximum<uint32_t>(), st);
+        });
         hipLaunchKernelGGL(kScatterRank, dim3(grid), dim3(kTB), 0, st, vb.current(), g.ptr, N, isa.ptr);
         hipLaunchKernelGGL(kPairKeys, dim3(grid), dim3(kTB), 0, st, isa.ptr, N, h, kb.current(), vb.current());
         SH_HIP(hipGetLastError());
-        tb = tmp.cap;
-        SH_HIP(rocprim::radix_sort_pairs(tmp.ptr, tb, kb, vb, (size_t)N, 0, 64, st));
+        sortPairs(64);
         h *= 2;
     }
     if (vb.current() != dSA)
@@ -383,13 +382,11 @@ void buildLines(const uint8_t* dBwt, uint64_t N, const uint64_t* dSampled, DevBu
     hipLaunchKernelGGL(kLinesLocal, dim3(grid), dim3(kTB), 0, st, dBwt, N, dSampled, lines.ptr, counts.ptr);
     SH_HIP(hipGetLastError());
     SH_HIP(hipMemsetAsync(counts.ptr + nb, 0, sizeof(Cnt6), st));
-    size_t tb = 0;
     Cnt6 zero = {{0, 0, 0, 0, 0, 0}};
-    SH_HIP(rocprim::exclusive_scan(nullptr, tb, counts.ptr, counts.ptr, zero, (size_t)nb + 1, Cnt6Plus(), st));
     DevBuf<char> tmp;
-    tmp.reserve(tb + 256);
-    tb = tmp.cap;
-    SH_HIP(rocprim::exclusive_scan(tmp.ptr, tb, counts.ptr, counts.ptr, zero, (size_t)nb + 1, Cnt6Plus(), st));
+    withTemp(tmp, [&](void* temp, size_t& bytes) {
+        return rocprim::exclusive_scan(temp, bytes, counts.ptr, counts.ptr, zero, (size_t)nb + 1, Cnt6Plus(), st);
+    });
     hipLaunchKernelGGL(kLinesCounts, dim3(grid), dim3(kTB), 0, st, lines.ptr, counts.ptr, nb);
     SH_HIP(hipGetLastError());
     Cnt6 tot;

@@ -6,17 +6,16 @@
 //
 //   kLociHeads    record i starts a locus?           -> flag[i]
 //   rocPRIM scan  inclusive sum of the flags         -> num[i] = locus of i, + 1; num[rows - 1] = loci
+//                 (hits.hip scanFlagsCount)
 //   kLociReduce   min over each locus of (err, i)    -> best[locus]
 //   kLociGather   the representatives, in order      -> scratch, copied back over the batch
+//                 (hits.hip replaceBatch)
 //
 // The predicate and the key are loci_core.h's.
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstring>
-
-#include <rocprim/rocprim.hpp>
 
 #include "loci_core.h"
 #include "search_device.h"
@@ -91,71 +90,32 @@ __global__ void kLociGather(const sahara_hit* __restrict__ h, const unsigned lon
         dst[l] = h[lociKeyIndex(best[l])];
 }
 
-// The per-query segments of the representatives (limitBatch reads them when
-// --max_hits follows): qoff[q] = the first of the `loci` records whose qid is
-// not below qidBase + q, qoff[nq] = loci. One binary search per query.
-__global__ void kLociSegments(const sahara_hit* __restrict__ h, uint64_t loci, uint64_t qidBase, uint32_t nq,
-                              uint64_t* __restrict__ qoff) {
-    for (uint32_t q = blockIdx.x * blockDim.x + threadIdx.x; q <= nq; q += gridDim.x * blockDim.x) {
-        uint64_t lo = 0, hi = loci;
-        while (lo < hi) {
-            const uint64_t mid = lo + (hi - lo) / 2;
-            if (h[mid].qid < qidBase + q) lo = mid + 1;
-            else hi = mid;
-        }
-        qoff[q] = lo;
-    }
-}
-
 }  // namespace
 
-// qoff[0..nq] over the n sorted records h (kLociSegments): what the loci stage and the pair stage
-// (pairs.hip) each leave for limitBatch when they dropped records
-void launchHitSegments(const sahara_hit* h, uint64_t n, uint64_t qidBase, uint32_t nq, uint64_t* qoff, hipStream_t st) {
-    const uint32_t qblocks = std::min<uint32_t>(nq / 256 + 1, 16384);
-    hipLaunchKernelGGL(kLociSegments, dim3(qblocks), dim3(256), 0, st, h, n, qidBase, nq, qoff);
-    SH_HIP(hipGetLastError());
-}
-
-// One batch's whole hits (out, rows; canonical order) reduced in place to one
-// record per locus for `window`; returns the records kept. Host-synchronous
-// like limitBatch: the count sizes the rest of the batch's chain, and comes
-// back through hostKept (8 B of pinned memory). qoff != nullptr: the batch's
-// per-query segments (nq + 1 offsets, first qid qidBase) are rewritten for
-// the records kept.
-uint64_t lociBatch(sahara_hit* out, uint64_t rows, uint32_t window, uint64_t* qoff, uint32_t nq, uint64_t qidBase,
-                   LociBufs& B, DevBuf<sahara_hit>& buf, DevBuf<char>& tmp, uint64_t* hostKept, hipStream_t st) {
-    if (rows == 0) return 0;
+// The batch (search.h BatchView: whole hits in canonical order) reduced in
+// place to one record per locus for `window`. Host-synchronous: the locus
+// count sizes the rest of the batch's chain.
+void lociBatch(BatchView& v, uint32_t window, LociBufs& B) {
+    const uint64_t rows = v.rows;
+    if (rows == 0) return;
     if (rows >= (1ull << 32)) throw Error("more than 2^32 hits in one batch of patterns");  // (the key's index)
-    auto room = [&](auto& b, uint64_t n) {
-        if (b.cap < n) b.reserve(n + n / 4 + 1024);
-    };
     room(B.flag, rows);
     room(B.num, rows);
     const uint32_t blocks = (uint32_t)std::min<uint64_t>((rows + 255) / 256, 8192);
-    hipLaunchKernelGGL(kLociHeads, dim3(blocks), dim3(256), 0, st, out, rows, window, B.flag.ptr);
+    hipLaunchKernelGGL(kLociHeads, dim3(blocks), dim3(256), 0, v.st, v.hits, rows, window, B.flag.ptr);
     SH_HIP(hipGetLastError());
-    size_t bytes = 0;
-    SH_HIP(rocprim::inclusive_scan(nullptr, bytes, B.flag.ptr, B.num.ptr, (size_t)rows, rocprim::plus<uint32_t>(), st));
-    tmp.reserve(bytes + 256);
-    SH_HIP(rocprim::inclusive_scan(tmp.ptr, bytes, B.flag.ptr, B.num.ptr, (size_t)rows, rocprim::plus<uint32_t>(), st));
-    *hostKept = 0;  // (the count is 32 bits: the low half of the word)
-    SH_HIP(hipMemcpyAsync(hostKept, B.num.ptr + (rows - 1), 4, hipMemcpyDeviceToHost, st));
-    SH_HIP(hipStreamSynchronize(st));
-    const uint64_t loci = *hostKept;
+    const uint64_t loci = scanFlagsCount(B.flag.ptr, B.num.ptr, v);
     if (loci == 0 || loci > rows) throw Error("loci: the locus count is out of range (internal)");
-    if (loci == rows) return rows;  // every record is a locus of its own: nothing to drop, the segments stand
+    if (loci == rows) return;  // every record is a locus of its own: nothing to drop, the segments stand
     room(B.best, loci);
-    room(buf, loci);
-    SH_HIP(hipMemsetAsync(B.best.ptr, 0xFF, loci * sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(kLociReduce, dim3(blocks), dim3(256), 0, st, out, B.num.ptr, rows, B.best.ptr);
+    room(v.scratch, loci);
+    SH_HIP(hipMemsetAsync(B.best.ptr, 0xFF, loci * sizeof(unsigned long long), v.st));
+    hipLaunchKernelGGL(kLociReduce, dim3(blocks), dim3(256), 0, v.st, v.hits, B.num.ptr, rows, B.best.ptr);
     SH_HIP(hipGetLastError());
     const uint32_t gblocks = (uint32_t)std::min<uint64_t>((loci + 255) / 256, 8192);
-    hipLaunchKernelGGL(kLociGather, dim3(gblocks), dim3(256), 0, st, out, B.best.ptr, loci, buf.ptr);
+    hipLaunchKernelGGL(kLociGather, dim3(gblocks), dim3(256), 0, v.st, v.hits, B.best.ptr, loci, v.scratch.ptr);
     SH_HIP(hipGetLastError());
-    SH_HIP(hipMemcpyAsync(out, buf.ptr, loci * sizeof(sahara_hit), hipMemcpyDeviceToDevice, st));
-    if (qoff) launchHitSegments(out, loci, qidBase, nq, qoff, st);
-    return loci;
+    replaceBatch(v, loci);
 }
 
 }  // namespace sahara

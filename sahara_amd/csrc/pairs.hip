@@ -5,8 +5,8 @@
 // hit, as in loci.hip: a query inside a repeat has 10^4..10^5 rows.
 //
 //   kPairFlags    record i has a mate? one lower bound   -> flag[i]
-//   rocPRIM scan  inclusive sum of the flags             -> num[i]; num[rows - 1] = kept
-//   kPairGather   the kept records, in order             -> scratch, copied back over the batch;
+//   rocPRIM scan  inclusive sum of the flags             -> num[i]; num[rows - 1] = kept (hits.hip scanFlagsCount)
+//   kPairGather   the kept records, in order             -> scratch, copied back over the batch (replaceBatch);
 //                 the pairs among them                   -> one counter
 //
 // A pair's four qids lie in one batch (pass_plan.h, granularity 4), so the
@@ -15,9 +15,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstring>
-
-#include <rocprim/rocprim.hpp>
 
 #include "pairs_core.h"
 #include "search_device.h"
@@ -32,10 +29,9 @@ struct HitAt {
 
 // One lower bound per record, over the partner query's segment
 // [qoff[p], qoff[p + 1]) of the batch's per-query offsets (p = partner -
-// qidBase): two dependent loads in front, then a handful of levels. qoff ==
-// nullptr (SAHARA_PAIRS_NARROW=0): over the whole batch, some 25 levels whose
-// top ones touch the same few records in every lane and stay in cache; that
-// measured 0.97 ms against 0.59 ms for 30.8M records.
+// qidBase): two dependent loads in front, then a handful of levels. (Over the
+// whole batch it is some 25 levels: 0.97 ms against 0.59 ms for 30.8M records,
+// DESIGN.md §3.10.)
 __global__ __launch_bounds__(256) void kPairFlags(const sahara_hit* __restrict__ h, uint64_t n, uint64_t dmin,
                                                   uint64_t dmax, const uint64_t* __restrict__ qoff, uint64_t qidBase,
                                                   uint32_t nq, uint32_t* __restrict__ flag) {
@@ -43,13 +39,11 @@ __global__ __launch_bounds__(256) void kPairFlags(const sahara_hit* __restrict__
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
         const sahara_hit x = h[i];
         uint64_t first = 0, last = n;
-        if (qoff) {
-            const uint64_t p = pairPartner(x.qid) - qidBase;  // (qidBase is a multiple of 4: no wrap)
-            if (p < nq) {
-                first = qoff[p];
-                last = min(qoff[p + 1], n);
-                first = min(first, last);
-            }
+        const uint64_t p = pairPartner(x.qid) - qidBase;  // (qidBase is a multiple of 4: no wrap)
+        if (p < nq) {
+            first = qoff[p];
+            last = min(qoff[p + 1], n);
+            first = min(first, last);
         }
         flag[i] = pairKeeps(at, x.qid, x.seq_id, x.pos, dmin, dmax, first, last) ? 1u : 0u;
     }
@@ -110,63 +104,48 @@ __global__ __launch_bounds__(256) void kPairGather(const sahara_hit* __restrict_
 
 }  // namespace
 
-// flag[i] = record i of the n sorted records has a concordant mate among them (kPairFlags): the pair
-// stage's first step, and the mate rescue's (rescue.hip), whose anchors are the records without one
-void launchPairFlags(const sahara_hit* h, uint64_t n, uint64_t dmin, uint64_t dmax, const uint64_t* qoff,
-                     uint64_t qidBase, uint32_t nq, uint32_t* flag, hipStream_t st) {
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>((n + 255) / 256, 8192);
-    hipLaunchKernelGGL(kPairFlags, dim3(blocks), dim3(256), 0, st, h, n, dmin, dmax, qoff, qidBase, nq, flag);
+// flag[i] = record i of the batch has a concordant mate in it (kPairFlags): the pair stage's first
+// step, and the mate rescue's (rescue.hip), whose anchors are the records without one
+void launchPairFlags(const BatchView& v, uint64_t dmin, uint64_t dmax, uint32_t* flag) {
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>((v.rows + 255) / 256, 8192);
+    hipLaunchKernelGGL(kPairFlags, dim3(blocks), dim3(256), 0, v.st, v.hits, v.rows, dmin, dmax, v.qoff, v.q0, v.nq,
+                       flag);
     SH_HIP(hipGetLastError());
 }
 
-// One batch's whole hits (out, rows; canonical order, a pair's four qids all
-// in the batch) reduced in place to the hits with a concordant mate for
+// The batch (search.h BatchView: whole hits in canonical order, a pair's four
+// qids all in it) reduced in place to the hits with a concordant mate for
 // pattern length len and fragments in [minFrag, maxFrag] (maxFrag >= len: the
-// call is refused otherwise, capi.cpp); returns the records kept.
-// Host-synchronous like lociBatch: the count sizes the rest of the batch's
-// chain and comes back through hostKept (8 B of pinned memory). The number of
-// pairs that keep a hit arrives in *hostPairs (pinned as well) once `st` has
-// passed this call's last copy: the caller reads it after the batch's chain.
-// qoff: the batch's per-query segments (nq + 1 offsets, first qid qidBase) or
-// nullptr; narrow: the searches run within them; rewrite: they are written
-// again for the records kept where some were dropped (limitBatch reads them).
-uint64_t pairsBatch(sahara_hit* out, uint64_t rows, uint32_t len, uint32_t minFrag, uint32_t maxFrag, uint64_t* qoff,
-                    uint32_t nq, uint64_t qidBase, bool narrow, bool rewrite, PairsBufs& B, DevBuf<sahara_hit>& buf, DevBuf<char>& tmp,
-                    uint64_t* hostKept, uint64_t* hostPairs, hipStream_t st) {
+// call is refused otherwise, capi.cpp). Host-synchronous like lociBatch: the
+// kept count sizes the rest of the batch's chain. The number of pairs that
+// keep a hit arrives in *hostPairs (pinned) once v.st has passed this call's
+// last copy: the caller reads it after the batch's chain.
+void pairsBatch(BatchView& v, uint32_t len, uint32_t minFrag, uint32_t maxFrag, PairsBufs& B, uint64_t* hostPairs) {
     *hostPairs = 0;
-    if (rows == 0) return 0;
+    const uint64_t rows = v.rows;
+    if (rows == 0) return;
     if (rows >= (1ull << 32)) throw Error("more than 2^32 hits in one batch of patterns");  // (the 32-bit running count)
     if (maxFrag < len) throw Error("pairs: max_fragment is below the pattern length (internal)");
-    auto room = [&](auto& b, uint64_t n) {
-        if (b.cap < n) b.reserve(n + n / 4 + 1024);
-    };
     room(B.flag, rows);
     room(B.num, rows);
     B.pairs.reserve(1);
     const PairDist d = pairDist(len, minFrag, maxFrag);
     const uint32_t blocks = (uint32_t)std::min<uint64_t>((rows + 255) / 256, 8192);
-    launchPairFlags(out, rows, d.dmin, d.dmax, narrow ? (const uint64_t*)qoff : nullptr, qidBase, nq, B.flag.ptr, st);
-    size_t bytes = 0;
-    SH_HIP(rocprim::inclusive_scan(nullptr, bytes, B.flag.ptr, B.num.ptr, (size_t)rows, rocprim::plus<uint32_t>(), st));
-    tmp.reserve(bytes + 256);
-    SH_HIP(rocprim::inclusive_scan(tmp.ptr, bytes, B.flag.ptr, B.num.ptr, (size_t)rows, rocprim::plus<uint32_t>(), st));
-    *hostKept = 0;  // (the count is 32 bits: the low half of the word)
-    SH_HIP(hipMemcpyAsync(hostKept, B.num.ptr + (rows - 1), 4, hipMemcpyDeviceToHost, st));
-    SH_HIP(hipStreamSynchronize(st));
-    const uint64_t kept = *hostKept;
+    launchPairFlags(v, d.dmin, d.dmax, B.flag.ptr);
+    const uint64_t kept = scanFlagsCount(B.flag.ptr, B.num.ptr, v);
     if (kept > rows) throw Error("pairs: the kept count is out of range (internal)");
-    if (kept == 0) return 0;  // (no rows: limitBatch returns at once, nothing reads the segments)
-    SH_HIP(hipMemsetAsync(B.pairs.ptr, 0, sizeof(unsigned long long), st));
+    if (kept == 0) {  // (no rows: no later stage runs on them, nothing reads the segments)
+        v.rows = 0;
+        return;
+    }
+    SH_HIP(hipMemsetAsync(B.pairs.ptr, 0, sizeof(unsigned long long), v.st));
     const bool all = kept == rows;  // nothing to drop: the records and the segments stand, the pairs are counted
-    if (!all) room(buf, kept);
-    hipLaunchKernelGGL(kPairGather, dim3(blocks), dim3(256), 0, st, out, B.flag.ptr, B.num.ptr, rows,
-                       all ? nullptr : buf.ptr, B.pairs.ptr);
+    if (!all) room(v.scratch, kept);
+    hipLaunchKernelGGL(kPairGather, dim3(blocks), dim3(256), 0, v.st, v.hits, B.flag.ptr, B.num.ptr, rows,
+                       all ? nullptr : v.scratch.ptr, B.pairs.ptr);
     SH_HIP(hipGetLastError());
-    SH_HIP(hipMemcpyAsync(hostPairs, B.pairs.ptr, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    if (all) return rows;
-    SH_HIP(hipMemcpyAsync(out, buf.ptr, kept * sizeof(sahara_hit), hipMemcpyDeviceToDevice, st));
-    if (qoff && rewrite) launchHitSegments(out, kept, qidBase, nq, qoff, st);
-    return kept;
+    SH_HIP(hipMemcpyAsync(hostPairs, B.pairs.ptr, sizeof(unsigned long long), hipMemcpyDeviceToHost, v.st));
+    if (!all) replaceBatch(v, kept);
 }
 
 }  // namespace sahara

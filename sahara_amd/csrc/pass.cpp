@@ -1,7 +1,9 @@
 // pass.cpp — one pass of the search over the staged patterns: batches
 // through seeds, FM phase, text phase, locate, sort and decode on the
-// context's streams, and the pass over every part of a
-// multi-part index.
+// context's streams, then through the stages that are on
+// (loci, mate rescue, pairs, --max_hits: one driver, Pass::stages, over one
+// view of the batch) into the call's sink; and the pass
+// over every part of a multi-part index.
 #include <algorithm>
 #include <cstdlib>
 #include <chrono>
@@ -62,9 +64,7 @@ void checkPairsCall(const Ctx* c, uint64_t npat, uint32_t len) {
 }
 
 void run(Ctx* c, bool count) {
-    c->loci.stats = sahara_loci_stats{};  // of this call: the passes below add to them
-    c->pairs.stats = sahara_pairs_stats{};
-    c->rescue.stats = sahara_rescue_stats{};
+    c->stageStats = Ctx::StageStats{};  // of this call: the passes below add to them
     if (c->sk.staged) checkPairsCall(c, c->npat, c->m);
     if (c->more.empty()) return runOne(c, count);
     // (rounds mask a query by its rows in one part; "found" is decided across the parts: capi.cpp bestOnHost)
@@ -126,15 +126,11 @@ void runOne(Ctx* c, bool count) {
     auto t0 = std::chrono::steady_clock::now();
     sahara_stats S{};
     bool overflow = false;
-    const sahara_loci_stats lociBefore = c->loci.stats;  // (a multi-part call's earlier parts)
-    const sahara_pairs_stats pairsBefore = c->pairs.stats;
-    const sahara_rescue_stats rescueBefore = c->rescue.stats;
+    const Ctx::StageStats stagesBefore = c->stageStats;  // (a multi-part call's earlier parts)
     runPass(c, count, false, S, overflow);
     if (overflow) {
         S = sahara_stats{};
-        c->loci.stats = lociBefore;  // the batches finished before the overflow are redone
-        c->pairs.stats = pairsBefore;
-        c->rescue.stats = rescueBefore;
+        c->stageStats = stagesBefore;  // the batches finished before the overflow are redone
         runPass(c, count, true, S, overflow);
     }
     S.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -415,9 +411,7 @@ struct Pass {
     bool& overflow;
     hipStream_t sA, sB, sC, sD;          // FM phase; text; locate / sort; seeds (serial: all Ctx::st)
     uint32_t seenTask = 0, seenHit = 0;  // pipelined overflow: the caps the re-run needs
-    bool lociRan = false;                // the batch just finished ran the loci stage (finishCheck reads its span)
-    bool pairsRan = false;               // ... the pair stage (its span and its pairs count)
-    bool rescueRan = false;              // ... the mate rescue (its span)
+    bool stageRan[kStages] = {};         // by Stage: the batch just finished ran it (finishCheck reads its span)
 
     Ctx::Slot& slotOf(uint64_t b) const { return c->slot[b % Ctx::kSlots]; }
 
@@ -604,15 +598,38 @@ struct Pass {
         S.text_ms += ms;
     }
 
-    // locate: row offsets (exclusive scan of len), SA / LF locate, canonical
-    // sort into the device-resident output (whole hits, or compact records
-    // where the call's sink takes those), on stream sC. Needs the
-    // batch's counts (host waits for its text phase). Returns false on
+    // A batch after its text phase, on stream sC: totals and overflow check,
+    // locate and sort, the stages that are on, the sink. Returns false on
     // overflow; `finishCheck` then reads the locate flags and timings.
     bool finish(uint64_t b) {
         Ctx::Slot& sl = slotOf(b);
         const uint64_t q0 = P.bstart[b], nb = P.bstart[b + 1] - q0;
+        BatchRecord& rec = c->pinned.ptr[b];
         c->mark("finish", b);
+        if (!totals(sl, b, nb, rec)) return false;
+        const bool direct = locateSort(sl, rec, q0, nb);  // (then, as with no rows, no stage runs: no whole hits)
+        BatchView v{rec.rows && !direct ? c->out.ptr + c->nout : nullptr, rec.rows, c->qoff.ptr, (uint32_t)nb, q0,
+                    c->stageScratch, c->tmp, &rec.kept, sC, false};
+        stages(v, rec);
+        // the rows that leave decide where they go (never direct after a stage: the sort stands)
+        const BatchPlan d = decideBatch(batchIn(v.rows, nb));
+        if (d.needRecs && v.rows) growOut(c->outRecs, c->nout + v.rows, c->nout);  // (the rescue may have added rows)
+        SH_HIP(hipEventRecord(c->sortDone, sC));
+        c->batchQ0.push_back(q0);
+        c->batchEnd.push_back(c->nout + v.rows);
+        c->batchDirect.push_back(d.direct ? 1 : 0);
+        sinkBatch(q0, v.rows, d);
+        launchLocateFlagsOut(c->small.ptr + kLocFlags, &rec.locateFlags, sC);
+        SH_HIP(hipEventRecord(c->flagsDown, sC));
+        if (P.sleepy) SH_HIP(hipEventRecord(c->flagsDownSleep, sC));
+        c->nout += v.rows;
+        S.hits += v.rows;
+        return true;
+    }
+
+    // The batch's totals into its pinned record (the host waits for its text
+    // phase) and the overflow check: false when a work buffer was too small.
+    bool totals(Ctx::Slot& sl, uint64_t b, uint64_t nb, BatchRecord& rec) {
         // After the text phase, on sC (work on sB would wait for CU slots
         // between two text phases): the per-query row counts are scanned into
         // segment offsets right away, and one small kernel then writes the
@@ -629,7 +646,6 @@ struct Pass {
         uint32_t* const segCounts = c->small.ptr + kLocSegCounts;
         querySegments(sl.qcnt.ptr, (uint32_t)nb, c->qoff.ptr, c->partial.ptr, c->big.ptr, segCounts, c->huge.ptr,
                       segCounts + 1, sC);
-        BatchRecord& rec = c->pinned.ptr[b];
         launchBatchTotals(sl.small.ptr, sl.queues.ptr, c->qoff.ptr + nb, segCounts, rec.slot, sC);
         SH_HIP(hipEventRecord(P.sleepy ? c->totalsDownSleep : c->totalsDown, sC));
         if (P.sleepy) waitSleepy(c->totalsDownSleep, P.k.pollUs);
@@ -648,12 +664,36 @@ struct Pass {
             freeSlot(sl, sC);
             return false;
         }
+        S.cursors += rec.slot[kSwFilled];
+        if (rec.rows >= (1ull << 32)) throw Error("more than 2^32 located hits in one batch of patterns");
+        return true;
+    }
+
+    // What decideBatch (hit_route.h) is asked, twice per batch: before the
+    // sort with the sorted rows (direct, needRecs: neither depends on the rows
+    // when a stage is on), and after the last stage with the rows that leave.
+    BatchIn batchIn(uint64_t rows, uint64_t nb) const {
+        return {c->sk.route, c->sk.wholeFallback, c->sk.ok, c->nout, rows, nb, c->sk.cap, c->sk.limitN,
+                c->more.empty(), Ctx::kDownSlot, c->loci.on, c->pairs.on};
+    }
+
+    // A device-resident output of the call (c->out, c->outRecs) grown to hold
+    // `need` records, the first `keep` of what it holds kept
+    template <typename Buf>
+    void growOut(Buf& buf, uint64_t need, uint64_t keep) {
+        if (need <= buf.cap) return;
+        SH_HIP(hipStreamSynchronize(c->stF));  // sink copies may still read the old buffer
+        buf.growKeeping(std::max<size_t>(need + need / 2, 1024), std::min<size_t>(keep, buf.cap), sC);
+    }
+
+    // locate: SA / LF locate into the segments that `totals` scanned, then the
+    // canonical sort into the device-resident output: whole hits, or compact
+    // records where the call's sink takes those (then it returns true).
+    bool locateSort(Ctx::Slot& sl, const BatchRecord& rec, uint64_t q0, uint64_t nb) {
         // reserved slots incl. len-0 holes; a wave's last range may reach past
         // the capacity without having written there (no overflow flag)
         const uint64_t nh = std::min<uint64_t>(rec.slot[kSwHitCount], c->hitCap);
-        S.cursors += rec.slot[kSwFilled];
-        uint64_t rows = rec.rows;
-        if (rows >= (1ull << 32)) throw Error("more than 2^32 located hits in one batch of patterns");
+        const uint64_t rows = rec.rows;
         const uint32_t nbig = rec.nbig, nhuge = rec.nhuge;
         c->k0.reserve(std::max<uint64_t>(rows, 1));
         if (nhuge) c->k1.reserve(std::max<uint64_t>(rows, 1));
@@ -665,111 +705,73 @@ struct Pass {
         // them: the record is the sort key with the batch-local query in
         // front, so nothing is decoded and nothing of the batch goes into
         // c->out (Ctx::wholeHits expands it should a reader of c->out ask).
-        // Where the batch goes is decided here, once (hit_route.h).
-        auto decide = [&](uint64_t r) {
-            return decideBatch({c->sk.route, c->sk.wholeFallback, c->sk.ok, c->nout, r, nb, c->sk.cap, c->sk.limitN,
-                                c->more.empty(), Ctx::kDownSlot, c->loci.on, c->pairs.on});
-        };
-        BatchPlan d = decide(rows);
-        const uint64_t end = c->nout + rows;
-        auto growFor = [&](auto& buf) {  // a device-resident output of the call, kept as it grows
-            if (end <= buf.cap || rows == 0) return;  // (no rows: the sorts write nothing)
-            SH_HIP(hipStreamSynchronize(c->stF));  // sink copies may still read the old buffer
-            buf.growKeeping(std::max<size_t>(end + end / 2, 1024), std::min<size_t>(c->nout, buf.cap), sC);
-        };
-        if (d.needRecs) growFor(c->outRecs);
+        const BatchPlan d = decideBatch(batchIn(rows, nb));
+        const uint64_t end = rows ? c->nout + rows : 0;  // (no rows: the sorts write nothing, nothing grows)
+        if (d.needRecs) growOut(c->outRecs, end, c->nout);
         if (d.direct) {
             sortCompact(c->k0.ptr, c->k1.ptr, rows, c->qoff.ptr, (uint32_t)nb, c->big.ptr, nbig, c->huge.ptr, nhuge,
                         c->outRecs.ptr + c->nout, c->tmp.ptr, c->tmp.cap, sC);
             c->outStale = true;
         } else {
-            growFor(c->out);
+            growOut(c->out, end, c->nout);
             sortDecode(c->k0.ptr, c->k1.ptr, rows, c->qoff.ptr, (uint32_t)nb, c->big.ptr, nbig, c->huge.ptr, nhuge, q0,
                        c->I.dRecStarts.ptr, (uint32_t)c->I.recStarts.size(), c->out.ptr + c->nout, c->tmp.ptr,
                        c->tmp.cap, sC);
         }
-        // Loci (docs/semantics.md "Loci"): the batch's whole hits, sorted, cut
-        // to one record per locus where they lie; everything after it (the
-        // --max_hits cut, the copies, the sink) sees the representatives only.
-        lociRan = c->loci.on && rows != 0;
-        if (lociRan) {
-            sahara_loci_stats& L = c->loci.stats;
-            L.hits_in += rows;
-            ++L.batches;
-            SH_HIP(hipEventRecord(c->lociStart, sC));
-            // (the segments rewritten for whichever stage reads them next)
-            const bool segments = c->sk.limitN || (c->pairs.on && P.k.pairsNarrow) || c->rescue.on;
-            rows = lociBatch(c->out.ptr + c->nout, rows, c->loci.window, segments ? c->qoff.ptr : nullptr,
-                             (uint32_t)nb, q0, c->loci.bufs, c->limitBuf, c->tmp, &rec.kept, sC);
-            SH_HIP(hipEventRecord(c->lociDone, sC));
-            L.loci += rows;
-            d = decide(rows);  // (never direct, as below)
-        }
-        // Mate rescue (docs/semantics.md "Mate rescue"): the hits without a mate
-        // get their fragment windows scanned for the partner's pattern, and
-        // what that finds joins the batch's hits before the pair stage cuts
-        // them. The batch may grow here, by no more than it has anchors: c->out
-        // grows between the stage's halves, once the count is known, and keeps
-        // the batch's records.
-        rescueRan = c->rescue.on && c->pairs.on && rows != 0;
-        if (rescueRan) {
-            sahara_rescue_stats& R = c->rescue.stats;
-            ++R.batches;
-            SH_HIP(hipEventRecord(c->rescueStart, sC));
-            const RescueIn in{c->m, c->pairs.minFrag, c->pairs.maxFrag, c->rescue.maxErr, c->rescue.maxAnchors, c->edit,
-                              c->I.dRecStarts.ptr, (uint32_t)c->I.recStarts.size(), c->I.n, c->I.text3.ptr,
-                              c->pats3.ptr + q0 * c->patBlocks, c->patBlocks, c->qoff.ptr, (uint32_t)nb, q0,
-                              P.k.pairsNarrow};
-            RescueCounts n{};
-            rescueFind(c->out.ptr + c->nout, rows, in, c->rescue.bufs, c->tmp, n, sC);
-            if (const uint64_t need = c->nout + rows + n.rescued; need > c->out.cap) {
-                SH_HIP(hipStreamSynchronize(c->stF));  // sink copies may still read the old buffer
-                c->out.growKeeping(std::max<size_t>(need + need / 2, 1024), c->nout + rows, sC);
+        return d.direct;
+    }
+
+    // The stages that are on, in pass_plan.h's order, over the one view of the
+    // batch's whole hits: the sink sees what the last one left. A stage that
+    // is off, or finds no rows left at its turn, records no events and counts
+    // no batch. v.later tells a stage that changes the records whether to
+    // write their segments again (pass_plan.h, the segments rule). Each case
+    // holds what is the stage's own: the rule's numbers, its buffers, its counts.
+    void stages(BatchView& v, BatchRecord& rec) {
+        const StagesOn on = stagesOn(c->loci.on, c->pairs.on, c->rescue.on, c->sk.limitN != 0);
+        Ctx::StageStats& T = c->stageStats;
+        for (uint32_t s = 0; s < kStages; ++s) {
+            stageRan[s] = on.on[s] && v.rows != 0;
+            if (!stageRan[s]) continue;
+            v.later = laterStage(on, s);
+            const Ctx::StageStats::Figures f = T.figures(s);
+            if (f.batches) {
+                ++*f.batches;
+                SH_HIP(hipEventRecord(c->stageStart[s], sC));
             }
-            rows = rescueMerge(c->out.ptr + c->nout, rows, n.rescued, in, c->rescue.bufs, c->limitBuf, c->tmp, sC);
-            SH_HIP(hipEventRecord(c->rescueDone, sC));
-            R.anchors += n.anchors;
-            R.capped_queries += n.cappedQueries;
-            R.starts += n.starts;
-            R.rescued += n.rescued;
-            d = decide(rows);
-            if (d.needRecs && c->nout + rows > c->outRecs.cap) {  // (sized for the sorted rows above)
-                SH_HIP(hipStreamSynchronize(c->stF));
-                const uint64_t need = c->nout + rows;
-                c->outRecs.growKeeping(std::max<size_t>(need + need / 2, 1024), std::min<size_t>(c->nout, c->outRecs.cap), sC);
+            switch (s) {
+            case kStageLoci:  // docs/semantics.md "Loci": one record per locus
+                T.loci.hits_in += v.rows;
+                lociBatch(v, c->loci.window, c->loci.bufs);
+                T.loci.loci += v.rows;
+                break;
+            case kStageRescue: {
+                // docs/semantics.md "Mate rescue": the hits without a mate get their
+                // fragment windows scanned for the partner's pattern, and what that
+                // finds joins the batch's hits before the pair stage cuts them. The
+                // batch may grow here, by no more than it has anchors: c->out grows
+                // between the stage's halves, once the count is known, and keeps the
+                // batch's records.
+                const RescueIn in{c->m, c->pairs.minFrag, c->pairs.maxFrag, c->rescue.maxErr, c->rescue.maxAnchors,
+                                  c->edit, c->I.dRecStarts.ptr, (uint32_t)c->I.recStarts.size(), c->I.n,
+                                  c->I.text3.ptr, c->pats3.ptr + v.q0 * c->patBlocks, c->patBlocks};
+                const uint64_t r = rescueFind(v, in, c->rescue.bufs, T.rescue);
+                growOut(c->out, c->nout + v.rows + r, c->nout + v.rows);
+                v.hits = c->out.ptr + c->nout;
+                rescueMerge(v, r, c->rescue.bufs);
+                break;
             }
+            case kStagePairs:  // docs/semantics.md "Pairs": the hits with a mate in the batch, which holds whole pairs
+                T.pairs.hits_in += v.rows;
+                pairsBatch(v, c->m, c->pairs.minFrag, c->pairs.maxFrag, c->pairs.bufs, &rec.pairs);
+                T.pairs.kept += v.rows;
+                break;
+            case kStageLimit:  // --max_hits: this batch's queries keep their n best positions (search_n)
+                limitBatch(v, c->sk.limitN, c->limit);
+                break;
+            }
+            if (f.batches) SH_HIP(hipEventRecord(c->stageDone[s], sC));
         }
-        // Pairs (docs/semantics.md "Pairs"): of what is left, the hits with a
-        // concordant mate in the batch, which holds whole pairs (makePlan).
-        pairsRan = c->pairs.on && rows != 0;
-        if (pairsRan) {
-            sahara_pairs_stats& R = c->pairs.stats;
-            R.hits_in += rows;
-            ++R.batches;
-            SH_HIP(hipEventRecord(c->pairsStart, sC));
-            rows = pairsBatch(c->out.ptr + c->nout, rows, c->m, c->pairs.minFrag, c->pairs.maxFrag,
-                              c->sk.limitN || P.k.pairsNarrow ? c->qoff.ptr : nullptr, (uint32_t)nb, q0,
-                              P.k.pairsNarrow, c->sk.limitN != 0, c->pairs.bufs, c->limitBuf, c->tmp, &rec.kept, &rec.pairs, sC);
-            SH_HIP(hipEventRecord(c->pairsDone, sC));
-            R.kept += rows;
-            d = decide(rows);
-        }
-        if (c->sk.limitN) {  // --max_hits: this batch's queries keep their n best positions (search_n)
-            rows = limitBatch(c->out.ptr + c->nout, rows, c->qoff.ptr, (uint32_t)nb, c->sk.limitN, c->limitCnt,
-                              c->limitOff, c->limitBuf, c->tmp, &rec.kept, sC);
-            d = decide(rows);  // the rows kept are what leaves (never direct: the sort above stands)
-        }
-        SH_HIP(hipEventRecord(c->sortDone, sC));
-        c->batchQ0.push_back(q0);
-        c->batchEnd.push_back(c->nout + rows);
-        c->batchDirect.push_back(d.direct ? 1 : 0);
-        sinkBatch(q0, rows, d);
-        launchLocateFlagsOut(c->small.ptr + kLocFlags, &rec.locateFlags, sC);
-        SH_HIP(hipEventRecord(c->flagsDown, sC));
-        if (P.sleepy) SH_HIP(hipEventRecord(c->flagsDownSleep, sC));
-        c->nout += rows;
-        S.hits += rows;
-        return true;
     }
 
     // The call's host sink: the batch's hits (`rows` from c->nout on) go to
@@ -831,18 +833,13 @@ struct Pass {
         S.locate_ms += ms;
         SH_HIP(hipEventElapsedTime(&ms, c->locDone, c->sortDone));
         S.sort_ms += ms;
-        if (lociRan) {
-            SH_HIP(hipEventElapsedTime(&ms, c->lociStart, c->lociDone));
-            c->loci.stats.kernel_ms += ms;
-        }
-        if (rescueRan) {
-            SH_HIP(hipEventElapsedTime(&ms, c->rescueStart, c->rescueDone));
-            c->rescue.stats.kernel_ms += ms;
-        }
-        if (pairsRan) {  // (flagsDown has passed the stage's last copy, the one into the batch's record)
-            SH_HIP(hipEventElapsedTime(&ms, c->pairsStart, c->pairsDone));
-            c->pairs.stats.kernel_ms += ms;
-            c->pairs.stats.pairs += c->pinned.ptr[b].pairs;
+        for (uint32_t s = 0; s < kStages; ++s) {  // the stages that ran on the batch (finish(b + 1) records again after this)
+            double* const total = c->stageStats.figures(s).kernelMs;
+            if (!stageRan[s] || !total) continue;
+            SH_HIP(hipEventElapsedTime(&ms, c->stageStart[s], c->stageDone[s]));
+            *total += ms;
+            // (flagsDown has passed the pair stage's last copy, the one into the batch's record)
+            if (s == kStagePairs) c->stageStats.pairs.pairs += c->pinned.ptr[b].pairs;
         }
         c->mark("checked", b);
     }

@@ -34,7 +34,7 @@ inline std::vector<uint64_t> parseRamp(const char* e) {
 }
 
 struct PassKnobs {
-    bool pipeline, dump, chunkSeeds, kmerPos, seedTasks, pairsNarrow;
+    bool pipeline, dump, chunkSeeds, kmerPos, seedTasks;
     uint32_t fmLdsDepth, fmStealAt, stealAt, split, textSteps, refillAt, pollUs;
     uint32_t hitCap, taskCap;              // 0: unset
     unsigned long timerSlackNs;
@@ -101,9 +101,6 @@ inline PassKnobs readPassKnobs(bool verify) {
     // the hit and task buffers' first sizes (tests force overflow re-runs)
     if (auto v = num("SAHARA_HITCAP")) k.hitCap = (uint32_t)std::max(1L, *v);
     if (auto v = num("SAHARA_TASKCAP")) k.taskCap = (uint32_t)std::max(1L, *v);
-    // the pair stage's lower bounds: 1 within the partner query's segment, 0 (A/B) over the whole batch
-    // (pairs.hip kPairFlags; DESIGN.md §3.10 has both measured)
-    k.pairsNarrow = num("SAHARA_PAIRS_NARROW").value_or(1) != 0;
     k.batch = num("SAHARA_BATCH");        // maxBatchOf
     k.fmBpc = num("SAHARA_FM_BPC");       // workgroups per CU (pass.cpp makePlan)
     k.textBpc = num("SAHARA_TEXT_BPC");
@@ -208,6 +205,30 @@ inline WorstRound worstRound(const Rounds& rounds) {
         w.maxErr = std::max(w.maxErr, r.maxErr);
     }
     return w;
+}
+
+// The stages that a batch's sorted whole hits go through before they leave
+// the device, in the order they run (pass.cpp Pass::stages): loci (loci.hip),
+// the mate rescue (rescue.hip), pairs (pairs.hip), --max_hits (hits.hip
+// limitBatch). The rescue looks in the pair rule's window: it counts as on
+// only with pairs on.
+enum Stage : uint32_t { kStageLoci, kStageRescue, kStagePairs, kStageLimit, kStages };
+struct StagesOn {
+    bool on[kStages];
+};
+inline StagesOn stagesOn(bool loci, bool pairs, bool rescue, bool limit) {
+    return {{loci, rescue && pairs, pairs, limit}};
+}
+// The segments rule. When a stage starts, the batch's per-query segments
+// (qoff) describe the records it is given: the sort leaves them so, and a
+// stage that changed the records (loci or pairs dropped some, the rescue
+// added some) writes them again iff a later stage runs on the batch, which is
+// what this says (search.h BatchView::later, hits.hip replaceBatch). Every
+// stage after the first reads them.
+inline bool laterStage(const StagesOn& s, uint32_t stage) {
+    for (uint32_t i = stage + 1; i < kStages; ++i)
+        if (s.on[i]) return true;
+    return false;
 }
 
 // Everything a pass fixes before its first HIP call (pass.cpp makePlan);

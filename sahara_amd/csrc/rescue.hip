@@ -140,14 +140,6 @@ __global__ __launch_bounds__(kRescueWave) void kRescueScan(ScanArgs a) {
     }
 }
 
-struct HitLess {  // the canonical order
-    __host__ __device__ bool operator()(const sahara_hit& a, const sahara_hit& b) const {
-        if (a.qid != b.qid) return a.qid < b.qid;
-        if (a.seq_id != b.seq_id) return a.seq_id < b.seq_id;
-        if (a.pos != b.pos) return a.pos < b.pos;
-        return a.err < b.err;
-    }
-};
 struct HitSame {  // (two anchors that find one position find one e*)
     __host__ __device__ bool operator()(const sahara_hit& a, const sahara_hit& b) const {
         return a.qid == b.qid && a.seq_id == b.seq_id && a.pos == b.pos;
@@ -162,54 +154,51 @@ __global__ void kRescueCount(const sahara_hit* __restrict__ sorted, unsigned lon
 
 }  // namespace
 
-// The stage's first half: the anchors of one batch's whole hits (h, rows;
-// canonical order) found and scanned, the distinct rescued records left in
-// B.found in canonical order; counts.rescued says how many. Host-synchronous
-// like pairsBatch: the count sizes what the caller grows before the merge.
-void rescueFind(const sahara_hit* h, uint64_t rows, const RescueIn& in, RescueBufs& B, DevBuf<char>& tmp,
-                RescueCounts& counts, hipStream_t st) {
-    counts = RescueCounts{};
-    if (rows == 0) return;
+// The stage's first half: the anchors of the batch (search.h BatchView: whole
+// hits in canonical order) found and scanned, the distinct rescued records
+// left in B.found in canonical order and their number returned; the stage's
+// counts join `total`. Host-synchronous like pairsBatch: the number sizes
+// what the caller grows before the merge.
+uint64_t rescueFind(const BatchView& v, const RescueIn& in, RescueBufs& B, sahara_rescue_stats& total) {
+    const sahara_hit* const h = v.hits;
+    const uint64_t rows = v.rows;
+    const hipStream_t st = v.st;
+    if (rows == 0) return 0;
     if (rows >= (1ull << 32)) throw Error("more than 2^32 hits in one batch of patterns");  // (32-bit indices and sums)
-    if (!in.qoff) throw Error("rescue: the batch has no per-query segments (internal)");
     if (in.maxFrag < in.len || in.maxErr == 0 || in.maxErr > kAlignMaxErr || in.len > kAlignMaxLen)
         throw Error("rescue: a setting out of range reached the stage (internal)");
     const PairDist d = pairDist(in.len, in.minFrag, in.maxFrag);
     if (d.dmax - d.dmin >= kRescueMaxWindow) throw Error("rescue: the fragment window is too wide (internal)");
-    auto room = [&](auto& b, uint64_t n) {
-        if (b.cap < n) b.reserve(n + n / 4 + 1024);
-    };
     room(B.flag, rows);
     room(B.anchors, rows);
     B.words.reserve(kRescueWords);
     B.host.reserve(kRescueWords);
     SH_HIP(hipMemsetAsync(B.words.ptr, 0, kRescueWords * sizeof(unsigned long long), st));
-    launchPairFlags(h, rows, d.dmin, d.dmax, in.narrow ? in.qoff : nullptr, in.qidBase, in.nq, B.flag.ptr, st);
+    launchPairFlags(v, d.dmin, d.dmax, B.flag.ptr);
     const uint32_t blocks = (uint32_t)std::min<uint64_t>((rows + 255) / 256, 8192);
     hipLaunchKernelGGL(kRescueAnchorFlags, dim3(blocks), dim3(256), 0, st, h, rows, d.dmin, d.dmax, in.recStarts, in.nrec,
                        in.textLen, B.flag.ptr);
     SH_HIP(hipGetLastError());
-    size_t bytes = 0;
     if (in.maxAnchors) {
         room(B.num, rows);
-        SH_HIP(rocprim::inclusive_scan(nullptr, bytes, B.flag.ptr, B.num.ptr, (size_t)rows, rocprim::plus<uint32_t>(), st));
-        tmp.reserve(bytes + 256);
-        SH_HIP(rocprim::inclusive_scan(tmp.ptr, bytes, B.flag.ptr, B.num.ptr, (size_t)rows, rocprim::plus<uint32_t>(), st));
-        hipLaunchKernelGGL(kRescueCap, dim3(blocks), dim3(256), 0, st, h, rows, B.num.ptr, in.qoff, in.qidBase, in.nq,
+        withTemp(v.tmp, [&](void* temp, size_t& bytes) {
+            return rocprim::inclusive_scan(temp, bytes, B.flag.ptr, B.num.ptr, (size_t)rows, rocprim::plus<uint32_t>(), st);
+        });
+        hipLaunchKernelGGL(kRescueCap, dim3(blocks), dim3(256), 0, st, h, rows, B.num.ptr, v.qoff, v.q0, v.nq,
                            in.maxAnchors, B.flag.ptr, B.words.ptr + kRwCapped);
         SH_HIP(hipGetLastError());
     }
     const rocprim::counting_iterator<uint32_t> index(0u);
-    SH_HIP(rocprim::select(nullptr, bytes, index, B.flag.ptr, B.anchors.ptr, B.words.ptr + kRwAnchors, (size_t)rows, st));
-    tmp.reserve(bytes + 256);
-    SH_HIP(rocprim::select(tmp.ptr, bytes, index, B.flag.ptr, B.anchors.ptr, B.words.ptr + kRwAnchors, (size_t)rows, st));
+    withTemp(v.tmp, [&](void* temp, size_t& bytes) {
+        return rocprim::select(temp, bytes, index, B.flag.ptr, B.anchors.ptr, B.words.ptr + kRwAnchors, (size_t)rows, st);
+    });
     SH_HIP(hipMemcpyAsync(B.host.ptr, B.words.ptr, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     SH_HIP(hipStreamSynchronize(st));
     const uint64_t na = B.host.ptr[kRwAnchors];
-    counts.cappedQueries = B.host.ptr[kRwCapped];
+    total.capped_queries += B.host.ptr[kRwCapped];
     if (na > rows) throw Error("rescue: the anchor count is out of range (internal)");
-    counts.anchors = na;
-    if (na == 0) return;
+    total.anchors += na;
+    if (na == 0) return 0;
     if (na > 0x7FFFFFFFull) throw Error("rescue: too many anchors in one batch of patterns");
     room(B.found, na);
     room(B.sorted, na);
@@ -223,8 +212,8 @@ void rescueFind(const sahara_hit* h, uint64_t rows, const RescueIn& in, RescueBu
     a.text3Bytes = (uint32_t)std::min<uint64_t>(text3Blocks(in.textLen) * 16, 0xFFFFFF00ull);
     a.pats3 = in.pats3;
     a.patBlocks = in.patBlocks;
-    a.qidBase = in.qidBase;
-    a.nq = in.nq;
+    a.qidBase = v.q0;
+    a.nq = v.nq;
     a.m = in.len;
     a.maxErr = in.maxErr;
     a.edit = in.edit ? 1u : 0u;
@@ -235,38 +224,35 @@ void rescueFind(const sahara_hit* h, uint64_t rows, const RescueIn& in, RescueBu
     const size_t lds = alignTableBytes(in.maxErr, in.edit);
     hipLaunchKernelGGL(kRescueScan, dim3((unsigned)na), dim3(kRescueWave), lds, st, a);
     SH_HIP(hipGetLastError());
-    SH_HIP(rocprim::merge_sort(nullptr, bytes, B.found.ptr, B.sorted.ptr, (size_t)na, HitLess(), st));
-    tmp.reserve(bytes + 256);
-    SH_HIP(rocprim::merge_sort(tmp.ptr, bytes, B.found.ptr, B.sorted.ptr, (size_t)na, HitLess(), st));
-    SH_HIP(rocprim::unique(nullptr, bytes, B.sorted.ptr, B.found.ptr, B.words.ptr + kRwDistinct, (size_t)na, HitSame(), st));
-    tmp.reserve(bytes + 256);
-    SH_HIP(rocprim::unique(tmp.ptr, bytes, B.sorted.ptr, B.found.ptr, B.words.ptr + kRwDistinct, (size_t)na, HitSame(), st));
+    withTemp(v.tmp, [&](void* temp, size_t& bytes) {
+        return rocprim::merge_sort(temp, bytes, B.found.ptr, B.sorted.ptr, (size_t)na, HitLess(), st);
+    });
+    withTemp(v.tmp, [&](void* temp, size_t& bytes) {
+        return rocprim::unique(temp, bytes, B.sorted.ptr, B.found.ptr, B.words.ptr + kRwDistinct, (size_t)na, HitSame(), st);
+    });
     hipLaunchKernelGGL(kRescueCount, dim3(1), dim3(1), 0, st, B.found.ptr, B.words.ptr);
     SH_HIP(hipGetLastError());
     SH_HIP(hipMemcpyAsync(B.host.ptr, B.words.ptr, kRescueWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     SH_HIP(hipStreamSynchronize(st));
-    counts.starts = B.host.ptr[kRwStarts];
+    total.starts += B.host.ptr[kRwStarts];
     const uint64_t r = B.host.ptr[kRwRescued];
     if (r > na) throw Error("rescue: the rescued count is out of range (internal)");
-    counts.rescued = r;
+    total.rescued += r;
+    return r;
 }
 
 // The second half: the r records rescueFind left in B.found merged into the
-// batch's (h, rows; room for rows + r records), the per-query segments
-// written again; returns the records there are then. H and R share no
-// position (a record at a rescued one would have been the anchor's mate): a
-// plain merge keeps the canonical order.
-uint64_t rescueMerge(sahara_hit* h, uint64_t rows, uint64_t r, const RescueIn& in, RescueBufs& B, DevBuf<sahara_hit>& buf,
-                     DevBuf<char>& tmp, hipStream_t st) {
-    if (r == 0) return rows;
-    if (buf.cap < rows + r) buf.reserve(rows + r + (rows + r) / 4 + 1024);
-    size_t bytes = 0;
-    SH_HIP(rocprim::merge(nullptr, bytes, h, B.found.ptr, buf.ptr, (size_t)rows, (size_t)r, HitLess(), st));
-    tmp.reserve(bytes + 256);
-    SH_HIP(rocprim::merge(tmp.ptr, bytes, h, B.found.ptr, buf.ptr, (size_t)rows, (size_t)r, HitLess(), st));
-    SH_HIP(hipMemcpyAsync(h, buf.ptr, (rows + r) * sizeof(sahara_hit), hipMemcpyDeviceToDevice, st));
-    launchHitSegments(h, rows + r, in.qidBase, in.nq, in.qoff, st);
-    return rows + r;
+// batch's (v.hits has room for v.rows + r records). H and R share no position
+// (a record at a rescued one would have been the anchor's mate): a plain
+// merge keeps the canonical order.
+void rescueMerge(BatchView& v, uint64_t r, RescueBufs& B) {
+    if (r == 0) return;
+    const uint64_t rows = v.rows;
+    room(v.scratch, rows + r);
+    withTemp(v.tmp, [&](void* temp, size_t& bytes) {
+        return rocprim::merge(temp, bytes, v.hits, B.found.ptr, v.scratch.ptr, (size_t)rows, (size_t)r, HitLess(), v.st);
+    });
+    replaceBatch(v, rows + r);
 }
 
 }  // namespace sahara

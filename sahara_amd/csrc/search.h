@@ -104,20 +104,21 @@ constexpr uint32_t kQueueWords = 256;
 enum QueueAt : uint32_t { kQueueSeeds = 0, kQueueSeedTasks = kQueueWords, kQueueFmTasks = 2 * kQueueWords,
                          kQueuesWords = 3 * kQueueWords };
 // One batch's record in pinned host memory (Ctx::pinned), written by
-// kBatchTotals (words 0-11), kLocateFlagsOut (7), lociBatch, pairsBatch and limitBatch (12-13, one after
-// the other) and pairsBatch (14-15)
+// kBatchTotals (words 0-11), kLocateFlagsOut (7), the batch's stages through BatchView::kept (12-13, one
+// after the other) and pairsBatch (14-15)
 struct BatchRecord {
     uint32_t slot[7];      // the slot's counters, by SlotWord
     uint32_t locateFlags;  // the locate chain's flags word (kFlagLocate)
     uint64_t rows;         // the batch's row total
     uint32_t nbig, nhuge;  // long / huge segments
-    uint64_t kept;         // rows the loci stage keeps, then the pair stage, then --max_hits (each read before the next is written)
+    uint64_t kept;         // the word every stage reads its count back through (scanFlagsCount, limitBatch): the
+                           // host has read one stage's before the next stage writes its own
     uint64_t pairs;        // pairs that keep a hit (the pair stage; read after the batch's chain)
 };
 static_assert(sizeof(BatchRecord) == 64 && offsetof(BatchRecord, slot) == 0 &&
               offsetof(BatchRecord, locateFlags) == 4 * 7 && offsetof(BatchRecord, rows) == 4 * kSlotWords &&
               offsetof(BatchRecord, nbig) == 4 * 10 && offsetof(BatchRecord, nhuge) == 4 * 11 &&
-              offsetof(BatchRecord, kept) == 4 * 12, "BatchRecord is what kBatchTotals, lociBatch, pairsBatch and limitBatch write");
+              offsetof(BatchRecord, kept) == 4 * 12, "BatchRecord is what kBatchTotals and the batch's stages write");
 
 // work counters of count mode (sahara_stats; Ctx::counters)
 constexpr uint32_t kCounters = 56;
@@ -260,10 +261,6 @@ void launchInterleaveRC(const uint8_t* reads, uint64_t r0, uint64_t r1, uint32_t
 void launchDigest(const sahara_hit* h, uint64_t n, unsigned long long* out, hipStream_t st);
 void launchCopyHits(const sahara_hit* h, uint64_t n, uint64_t qidOffset, sahara_hit* dst, hipStream_t st);
 void launchOffsetSeq(const sahara_hit* in, uint64_t n, uint64_t rec0, sahara_hit* out, hipStream_t st);
-// --max_hits on the device: one batch's hits limited in place, kept rows returned
-uint64_t limitBatch(sahara_hit* out, uint64_t rows, const uint64_t* qoff, uint32_t nq, uint32_t n,
-                    DevBuf<uint32_t>& kcnt, DevBuf<uint64_t>& koff, DevBuf<sahara_hit>& buf, DevBuf<char>& tmp,
-                    uint64_t* hostKept, hipStream_t st);
 // key / index buffers of the multi-part merge (kept by the context)
 struct MergeBufs {
     DevBuf<uint64_t> k0, k1;
@@ -277,36 +274,38 @@ void launchCompactHits(const sahara_hit* h, uint64_t n, uint64_t qidBase, const 
 void launchExpandRecs(const uint64_t* recs, uint64_t n, uint64_t qidBase, const uint64_t* starts, uint32_t nrec,
                       sahara_hit* out, hipStream_t st);
 
-// ---- loci.hip: one batch's whole hits cut to one record per locus (docs/semantics.md "Loci")
+// ---- The stages between a batch's sort and its sink, in pass_plan.h's order (loci.hip, rescue.hip,
+// pairs.hip, limitBatch in hits.hip). Each works in place on one view of the batch, is host-synchronous
+// (a count comes back through the view's pinned word and sizes what follows) and leaves the view's records
+// and count as the next stage, or the sink, takes them.
+struct BatchView {
+    sahara_hit* hits;             // the batch's whole hits, canonical order ...
+    uint64_t rows;                // ... and their count: both are what the last stage left
+    uint64_t* qoff;               // their per-query segments (nq + 1 offsets): current whenever a stage starts
+    uint32_t nq;                  // (pass_plan.h, the segments rule)
+    uint64_t q0;                  // the batch's first qid
+    DevBuf<sahara_hit>& scratch;  // where a stage gathers the records it leaves (replaceBatch copies them back)
+    DevBuf<char>& tmp;            // rocPRIM's temporary storage
+    uint64_t* kept;               // 8 B of pinned host memory for the count a stage reads back (BatchRecord::kept)
+    hipStream_t st;
+    bool later;                   // a later stage runs on this batch (laterStage): the caller sets it per stage
+};
+// hits.hip. The end of a stage that changed the records: the n it left in v.scratch go back over the batch
+// and are its rows; the segments are written again for them iff v.later (kLociSegments: one binary search
+// per query). The one place that does either.
+void replaceBatch(BatchView& v, uint64_t n);
+// hits.hip. num = the inclusive sum of the v.rows flags (v.rows != 0); returns num[rows - 1], the flags
+// set, read back through v.kept after a sync of v.st (the stage's one host round trip)
+uint64_t scanFlagsCount(uint32_t* flag, uint32_t* num, BatchView& v);
+
+// loci.hip: the batch cut to one record per locus (docs/semantics.md "Loci")
 struct LociBufs {
     DevBuf<uint32_t> flag, num;  // per record: starts a locus; its locus + 1 (the flags' inclusive sum)
     DevBuf<unsigned long long> best;  // per locus: the least (err, index) key
 };
-// in place, kept records returned (host-synchronous, as limitBatch); qoff != nullptr: the batch's
-// per-query segments rewritten for the records kept (what limitBatch reads next)
-uint64_t lociBatch(sahara_hit* out, uint64_t rows, uint32_t window, uint64_t* qoff, uint32_t nq, uint64_t qidBase,
-                   LociBufs& B, DevBuf<sahara_hit>& buf, DevBuf<char>& tmp, uint64_t* hostKept, hipStream_t st);
-// qoff[q] = the first of the n sorted records whose qid is not below qidBase + q, for q in [0, nq] (loci.hip
-// kLociSegments): the per-query segments a stage that dropped records leaves for limitBatch
-void launchHitSegments(const sahara_hit* h, uint64_t n, uint64_t qidBase, uint32_t nq, uint64_t* qoff, hipStream_t st);
+void lociBatch(BatchView& v, uint32_t window, LociBufs& B);
 
-// ---- pairs.hip: one batch's whole hits cut to those with a concordant mate (docs/semantics.md "Pairs")
-struct PairsBufs {
-    DevBuf<uint32_t> flag, num;         // per record: has a mate; the flags' inclusive sum
-    DevBuf<unsigned long long> pairs;   // one word: the pairs that keep a hit
-};
-// in place, kept records returned (host-synchronous, as lociBatch); *hostPairs (pinned) gets the pairs with a
-// kept hit once st has passed the call; qoff: the batch's per-query segments or nullptr, searched within if
-// `narrow`, written again for the records kept if `rewrite`
-uint64_t pairsBatch(sahara_hit* out, uint64_t rows, uint32_t len, uint32_t minFrag, uint32_t maxFrag, uint64_t* qoff,
-                    uint32_t nq, uint64_t qidBase, bool narrow, bool rewrite, PairsBufs& B, DevBuf<sahara_hit>& buf, DevBuf<char>& tmp,
-                    uint64_t* hostKept, uint64_t* hostPairs, hipStream_t st);
-// flag[i] = record i of the n sorted records has a concordant mate among them (qoff: searched within the
-// partner's segment, or nullptr)
-void launchPairFlags(const sahara_hit* h, uint64_t n, uint64_t dmin, uint64_t dmax, const uint64_t* qoff,
-                     uint64_t qidBase, uint32_t nq, uint32_t* flag, hipStream_t st);
-
-// ---- rescue.hip: the mates that did not map, looked for beside the hits without one (docs/semantics.md
+// rescue.hip: the mates that did not map, looked for beside the hits without one (docs/semantics.md
 // "Mate rescue")
 struct RescueBufs {
     DevBuf<uint32_t> flag, num, anchors;     // per record: has a mate, then is an anchor; the anchor flags'
@@ -323,23 +322,32 @@ struct RescueIn {
     uint32_t nrec;
     uint64_t textLen;
     const uint4* text3;
-    const uint4* pats3;                      // the batch's patterns (qid qidBase first), patBlocks blocks each
+    const uint4* pats3;                      // the batch's patterns (qid v.q0 first), patBlocks blocks each
     uint32_t patBlocks;
-    uint64_t* qoff;                          // the batch's per-query segments (nq + 1 offsets), rewritten where records join
-    uint32_t nq;
-    uint64_t qidBase;
-    bool narrow;                             // kPairFlags searches within the partner's segment
 };
-struct RescueCounts {
-    uint64_t anchors, cappedQueries, starts, rescued;
+// The stage in two host-synchronous halves, so that the caller can grow the batch's buffer between them
+// (and point v.hits at it again): rescueFind scans the batch's anchors, leaves the distinct rescued records
+// in B.found, returns how many they are and adds its counts to `total`; rescueMerge merges those r records
+// into the batch, whose buffer has room for v.rows + r.
+uint64_t rescueFind(const BatchView& v, const RescueIn& in, RescueBufs& B, sahara_rescue_stats& total);
+void rescueMerge(BatchView& v, uint64_t r, RescueBufs& B);
+
+// pairs.hip: the batch cut to the hits with a concordant mate (docs/semantics.md "Pairs")
+struct PairsBufs {
+    DevBuf<uint32_t> flag, num;         // per record: has a mate; the flags' inclusive sum
+    DevBuf<unsigned long long> pairs;   // one word: the pairs that keep a hit
 };
-// The stage in two host-synchronous halves, so that the caller can grow the batch's buffer between them:
-// rescueFind scans the anchors of the batch's whole hits (h, rows; canonical order) and leaves the distinct
-// rescued records in B.found (counts.rescued of them); rescueMerge merges those r records into h, which has
-// room for rows + r, rewrites the per-query segments and returns the records there are then.
-void rescueFind(const sahara_hit* h, uint64_t rows, const RescueIn& in, RescueBufs& B, DevBuf<char>& tmp,
-                RescueCounts& counts, hipStream_t st);
-uint64_t rescueMerge(sahara_hit* h, uint64_t rows, uint64_t r, const RescueIn& in, RescueBufs& B, DevBuf<sahara_hit>& buf,
-                     DevBuf<char>& tmp, hipStream_t st);
+// *hostPairs (pinned) gets the pairs with a kept hit once v.st has passed the call
+void pairsBatch(BatchView& v, uint32_t len, uint32_t minFrag, uint32_t maxFrag, PairsBufs& B, uint64_t* hostPairs);
+// flag[i] = record i of the batch has a concordant mate in it, searched for within the partner query's
+// segment (the pair stage's first step, and the rescue's)
+void launchPairFlags(const BatchView& v, uint64_t dmin, uint64_t dmax, uint32_t* flag);
+
+// hits.hip: --max_hits n, the batch's queries cut to their n best positions
+struct LimitBufs {
+    DevBuf<uint32_t> cnt;   // per query: the records it keeps
+    DevBuf<uint64_t> off;   // ... their exclusive sum
+};
+void limitBatch(BatchView& v, uint32_t n, LimitBufs& B);
 
 }  // namespace sahara

@@ -1,7 +1,8 @@
 // search_device.h — device-side pieces that the kernel units (search_fm.hip,
-// search_text.hip, locate_sort.hip, hits.hip) share: global-memory accesses
-// that say so, the per-wave slot reservation of the append-only outputs, the
-// striped work queue, the plan of an in-wave steal and the decode of a sorted key.
+// search_text.hip, locate_sort.hip, hits.hip and the stage files) share:
+// global-memory accesses that say so, the per-wave slot reservation of the
+// append-only outputs, the striped work queue, the plan of an in-wave steal,
+// the decode of a sorted key and the canonical order of hit records.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -153,6 +154,17 @@ __device__ __forceinline__ sahara_hit decodeKey(uint64_t k, uint64_t qid, const 
     h.pos = gpos - starts[lo];
     return h;
 }
+
+// ---- the canonical order of hit records (the comparator of the rocPRIM
+// sorts and merges that work on whole hits)
+struct HitLess {
+    __host__ __device__ bool operator()(const sahara_hit& a, const sahara_hit& b) const {
+        if (a.qid != b.qid) return a.qid < b.qid;
+        if (a.seq_id != b.seq_id) return a.seq_id < b.seq_id;
+        if (a.pos != b.pos) return a.pos < b.pos;
+        return a.err < b.err;
+    }
+};
 
 }  // namespace
 }  // namespace sahara

@@ -1,6 +1,7 @@
 // The HIP-free part of a pass's plan (pass_plan.h) against values worked out
 // by hand from the rules it states (test_host_pool.py): batch boundaries, the
-// ramp lists, the text window and stack sizes, the batch size, the knobs.
+// ramp lists, the text window and stack sizes, the batch size, the stage order
+// and the segments rule, the knobs.
 #include <cstdio>
 #include <cstdlib>
 
@@ -110,6 +111,38 @@ int main() {
     CHECK(maxBatchOf(1L << 40, false, 1, true) == 1ull << 27);  // compact records
     CHECK(maxBatchOf(std::nullopt, false, 1, true) == 1ull << 22);
     CHECK(firstWorkCap(1) == 1u << 20 && firstWorkCap(1ull << 21) == 1u << 24 && firstWorkCap(1ull << 40) == 1u << 30);
+    // The stages of a batch's sorted hits: their order, which of them are on,
+    // and "a later stage runs" (the one rule for rewriting the per-query
+    // segments) against the three expressions that decided it per stage
+    // before, written out as they stood, with the pair stage's searches within
+    // the segments (`narrow`: the path that is left). All 12 valid settings.
+    CHECK(kStageLoci == 0 && kStageRescue == 1 && kStagePairs == 2 && kStageLimit == 3 && kStages == 4);
+    int settings = 0;
+    for (bool lociOn : {false, true})
+        for (int mates : {0, 1, 2})  // pairs off, pairs on, pairs + rescue
+            for (uint32_t limitN : {0u, 3u}) {
+                const bool pairsOn = mates >= 1, rescueOn = mates == 2, narrow = true;
+                const StagesOn on = stagesOn(lociOn, pairsOn, rescueOn, limitN != 0);
+                CHECK(on.on[kStageLoci] == lociOn && on.on[kStageRescue] == rescueOn);
+                CHECK(on.on[kStagePairs] == pairsOn && on.on[kStageLimit] == (limitN != 0));
+                // the loci call site: `segments ? qoff : nullptr`
+                const bool lociSegments = limitN || (pairsOn && narrow) || rescueOn;
+                CHECK(laterStage(on, kStageLoci) == lociSegments);
+                // the pairs call site: `limitN || narrow ? qoff : nullptr`, `rewrite = limitN != 0`
+                const bool pairsQoff = limitN || narrow, pairsRewrite = limitN != 0;
+                CHECK(laterStage(on, kStagePairs) == (pairsQoff && pairsRewrite));
+                // the rescue wrote them again whenever it added records: the pair stage follows it
+                if (rescueOn) CHECK(laterStage(on, kStageRescue));
+                CHECK(!laterStage(on, kStageLimit));
+                ++settings;
+            }
+    CHECK(settings == 12);
+    for (bool lociOn : {false, true})  // the rescue with pairs off counts as off
+        for (bool limit : {false, true}) {
+            const StagesOn on = stagesOn(lociOn, false, true, limit);
+            CHECK(!on.on[kStageRescue] && !on.on[kStagePairs]);
+            CHECK(laterStage(on, kStageLoci) == limit && laterStage(on, kStageRescue) == limit);
+        }
     // knobs: read on every call, defaults restored when unset
     for (const char* name : {"SAHARA_SPLIT", "SAHARA_PIPELINE", "SAHARA_BATCH", "SAHARA_RAMP", "SAHARA_FM_STEAL_AT",
                              "SAHARA_FM_LDS_DEPTH", "SAHARA_HITCAP", "SAHARA_REFILL_AT", "SAHARA_TEXT_STEPS",

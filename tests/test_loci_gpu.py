@@ -240,6 +240,30 @@ def test_compact_call_whose_sink_is_too_small(gpu_device, monkeypatch):
         gpu.close()
 
 
+def test_overflow_rerun_gives_the_same_rows_and_stats(gpu_device, monkeypatch):
+    """A hit buffer of 300 entries: the pipelined pass overflows and is redone
+    serially; the stage's figures are those of the batches that count."""
+    monkeypatch.setenv("SAHARA_BATCH", "257")
+    c = case()
+    gpu = gpu_of(gpu_device)
+    with loci_on(gpu, 2):
+        assert np.array_equal(hits_as_rows(sa.search_reads(gpu, c["reads"], c["scheme"])), want(2))
+        plain = gpu.loci_stats()
+    monkeypatch.setenv("SAHARA_HITCAP", "300")
+    monkeypatch.setenv("SAHARA_TASKCAP", "200")
+    small = sa.BiFMIndex.build(c["recs"], sigma=SIGMA, device=gpu_device)
+    try:
+        small.set_loci(2)
+        assert np.array_equal(hits_as_rows(sa.search_reads(small, c["reads"], c["scheme"])), want(2))
+        st = small.loci_stats()
+        assert small.stats()["pipelined"] == 0  # (the re-run is serial: the overflow happened)
+        for f in ("hits_in", "loci", "batches"):
+            assert st[f] == plain[f], (f, st, plain)
+        assert st["kernel_ms"] > 0
+    finally:
+        small.close()
+
+
 def test_fm_only_chain(gpu_device, monkeypatch):
     monkeypatch.setenv("SAHARA_BATCH", "257")
     c = case()

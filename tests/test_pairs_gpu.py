@@ -94,12 +94,9 @@ def test_every_entry_point_returns_the_paired_hits(gpu_device, monkeypatch, sett
         assert gpu.pairs_stats() == OFF, name
 
 
-@pytest.mark.parametrize("narrow", ["0", "1"])
-def test_both_search_ranges_and_ramped_batches(gpu_device, monkeypatch, narrow):
-    """The lower bound over the whole batch and within the partner query's
-    segment (SAHARA_PAIRS_NARROW), with loci and --max_hits around it; ramps
-    whose entries are no multiples of 4."""
-    monkeypatch.setenv("SAHARA_PAIRS_NARROW", narrow)
+def test_ramped_batches_with_loci_and_max_hits_around(gpu_device, monkeypatch):
+    """The lower bound within the partner query's segment, with loci and
+    --max_hits around it; ramps whose entries are no multiples of 4."""
     monkeypatch.setenv("SAHARA_BATCH", "260")
     monkeypatch.setenv("SAHARA_RAMP", "6:9")
     monkeypatch.setenv("SAHARA_RAMP_END", "30:2")

@@ -10,10 +10,8 @@ Timed, best of 5 after one warm-up, all runs listed:
 
   a  pairs off
   b  pairs on, fragments [200, 500]
-  n  b with the lower bounds over the whole batch instead of the partner query's segment (SAHARA_PAIRS_NARROW=0)
   l  loci on (W = 2), pairs off: the yardstick stage on the same hits
   c  loci and pairs on
-  m  c with SAHARA_PAIRS_NARROW=0
 
 Each step runs in a process of its own under `timeout`, and prints one JSON
 line: hits out, the bytes of the records that crossed to the host, the search
@@ -21,7 +19,7 @@ call, sort_ms, and the stages' figures (sahara_gpu_pairs_stats,
 sahara_gpu_loci_stats). --lib selects another build of the library
 (SAHARA_HIP_LIB); a step that build cannot run is skipped.
 
-    python tools/bench_pairs.py [--lib PATH] [--steps a,b,n,l,c,m] [--out FILE]
+    python tools/bench_pairs.py [--lib PATH] [--steps a,b,l,c] [--out FILE]
 """
 import argparse
 import json
@@ -34,10 +32,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_LEN, N_PAIRS, READ_LEN, K, WINDOW = 100_000_000, 1_000_000, 100, 2, 2
 MIN_FRAGMENT, MAX_FRAGMENT = 200, 500
 SPANS = ("seed_ms", "search_ms", "text_ms", "locate_ms", "sort_ms", "stage_ms", "output_ms")
-STEPS = {  # name: (pairs, loci, whole-batch lower bounds)
-    "a": (False, False, False), "b": (True, False, False), "n": (True, False, True),
-    "l": (False, True, False), "c": (True, True, False), "m": (True, True, True),
-}
+STEPS = {"a": (False, False), "b": (True, False), "l": (False, True), "c": (True, True)}  # name: (pairs, loci)
 
 
 def timed(call, runs, after):
@@ -84,13 +79,11 @@ def step(name, runs):
     sys.path.insert(0, ROOT)
     import sahara_amd as sa
 
-    pairs_on, loci_on, whole = STEPS[name]
+    pairs_on, loci_on = STEPS[name]
     has = hasattr(sa.lib(), "sahara_gpu_set_pairs")
     if pairs_on and not has:
         print(json.dumps({"step": name, "skipped": f"sahara_gpu_set_pairs missing in {sa.library_path()}"}))
         return
-    if whole:
-        os.environ["SAHARA_PAIRS_NARROW"] = "0"
     reads, idx = workload(sa)
     packed = sa.pack_reads(reads, 6, pinned=True)
     idx.prepare(2 * len(reads), READ_LEN)
@@ -119,14 +112,14 @@ def step(name, runs):
     print(json.dumps({"step": name, "build_id": sa.build_id(), "library": sa.library_path(), "reads": len(reads),
                       "patterns": 2 * len(reads), "read_len": READ_LEN,
                       "fragments": [MIN_FRAGMENT, MAX_FRAGMENT] if pairs_on else None,
-                      "window": WINDOW if loci_on else None, "narrow": pairs_on and not whole, "hits": hits, "download_bytes": 8 * hits,
+                      "window": WINDOW if loci_on else None, "hits": hits, "download_bytes": 8 * hits,
                       "reads_per_s": round(len(reads) / fig["best_s"]), **fig}))
 
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--lib", help="another build of libsahara_hip.so (SAHARA_HIP_LIB)")
-    ap.add_argument("--steps", default="a,b,n,l,c,m")
+    ap.add_argument("--steps", default="a,b,l,c")
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--timeout", type=int, default=240, help="seconds per step")
     ap.add_argument("--out", help="append the JSON lines to this file")
