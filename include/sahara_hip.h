@@ -358,6 +358,57 @@ typedef struct sahara_pairs_stats {    /* 40 B */
 /* ... of the context's last search call; zeros if pairs were off. */
 int  sahara_gpu_pairs_stats(void* ctx, sahara_pairs_stats* stats);
 
+/* --- best pairs (docs/semantics.md "Best pairs") ---
+ * With pairs on, a read pair that fits at several places keeps the hits of
+ * all of them, whatever they cost. With best pairs on as well, the pair stage
+ * ranks the concordant placements by the errors of both mates: a hit i of
+ * query q has the score m(i) = err(i) + the least err among its concordant
+ * mates, a pair has the best total s1 = the least score of its hits, and the
+ * stage keeps a hit iff it is the first record of its (qid, seq_id, pos) (its
+ * least err), has a mate and m(i) <= s1 + delta. Both orientations of a pair
+ * (A with rc B, B with rc A) compete in the one minimum; every kept hit has a
+ * kept mate. The cut runs inside the pair stage, on the device, per batch:
+ * after loci and the mate rescue, before --max_hits.
+ * Each pair of the call also gets a summary record: best = s1 (255: the pair
+ * keeps nothing), next = the least score above s1 among the pair's
+ * first-of-position hits (255: none), n_fwd / n_rev = the kept hits of its
+ * even / odd qids (saturating at 65535). With delta == 0, n_fwd == 1 &&
+ * n_rev == 1 says that the best placement is unique. (With loci off and edit
+ * distance a placement's neighbours at pos +- 1 make next == best + 1 almost
+ * always: next is meaningful with loci on.)
+ * on != 0: every later search call of this context is cut so; on == 0 (the
+ * default) restores the calls as they were. Refused with a negative code and
+ * a message: a NULL context, delta > SAHARA_BEST_PAIRS_MAX_DELTA, NULL stats.
+ * With best pairs on a search call is refused before any device work if pairs
+ * are off or if the index has several parts (a pair's best total over one
+ * part is not its best over all parts). A wide fragment window is not
+ * refused: a hit's work does not grow with the hits in its window beyond one
+ * read per 64 of them.
+ * While best pairs are on, sahara_pairs_stats.kept counts the hits that leave
+ * the stage (not those that merely have a mate); hits_in is unchanged. */
+#define SAHARA_BEST_PAIRS_MAX_DELTA 30
+int  sahara_gpu_set_best_pairs(void* ctx, int on, uint32_t delta);
+typedef struct sahara_pair_summary {   /* 8 B */
+    uint8_t  best, next;
+    uint16_t n_fwd, n_rev, reserved;
+} sahara_pair_summary;
+/* The last search call's summaries, one per pair in the call's order (pair p:
+ * qids 4p .. 4p + 3), into out[0 .. *n_pairs). out == NULL with capacity
+ * == 0 asks for the count alone: *n_pairs is set and 0 returned. Refused if
+ * that call ran without best pairs, if capacity is below the number of pairs
+ * or if out is NULL with a capacity. */
+int  sahara_gpu_pair_summary(void* ctx, sahara_pair_summary* out, uint64_t capacity, uint64_t* n_pairs);
+typedef struct sahara_best_pairs_stats {   /* 48 B */
+    uint64_t hits_in;       /* hits the pair stage took */
+    uint64_t kept;          /* hits it kept: the best placements' */
+    uint64_t pairs;         /* pairs with a kept hit */
+    uint64_t unique_pairs;  /* ... of them with n_fwd == 1 && n_rev == 1 */
+    uint64_t batches;       /* batches it ran on */
+    double   kernel_ms;     /* device time of the pair stage in best mode (HIP events), summed over batches */
+} sahara_best_pairs_stats;
+/* ... of the context's last search call; zeros if best pairs were off. */
+int  sahara_gpu_best_pairs_stats(void* ctx, sahara_best_pairs_stats* stats);
+
 /* --- mate rescue (docs/semantics.md "Mate rescue") ---
  * With pairs on, a hit whose partner query has no hit in its fragment window
  * is dropped, even where the partner lies there with a few errors more than

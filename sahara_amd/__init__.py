@@ -23,7 +23,7 @@ __all__ = [
     "BiFMIndex", "HIT_DTYPE", "search", "search_reads", "search_reads_compact", "CompactHits", "PackedReads",
     "pack_reads", "search_packed", "search_packed_compact", "search_best", "search_best_reads", "search_best_packed",
     "search_best_packed_compact", "ALIGN_DTYPE", "ALIGN_MAX_ERR", "ALIGN_NONE", "align", "align_packed_compact",
-    "align_stats", "cigar", "read_fasta", "search_scheme", "scheme_parts",
+    "align_stats", "cigar", "PAIR_SUMMARY_DTYPE", "PAIR_NONE", "read_fasta", "search_scheme", "scheme_parts",
     "scheme_generators",
     "scheme_counts", "synth_reference", "synth_reads", "interleave_rc", "load_fasta",
     "library_path", "lib", "SaharaError", "DNA5", "DNA4",
@@ -106,6 +106,16 @@ class PairsStats(C.Structure):
                 ("kernel_ms", C.c_double)]
 
 
+class BestPairsStats(C.Structure):
+    _fields_ = [("hits_in", C.c_uint64), ("kept", C.c_uint64), ("pairs", C.c_uint64), ("unique_pairs", C.c_uint64),
+                ("batches", C.c_uint64), ("kernel_ms", C.c_double)]
+
+
+# sahara_pair_summary (include/sahara_hip.h): one record per pair of a call with best pairs on
+PAIR_SUMMARY_DTYPE = np.dtype([("best", "u1"), ("next", "u1"), ("n_fwd", "<u2"), ("n_rev", "<u2"), ("reserved", "<u2")])
+PAIR_NONE = 255
+
+
 class RescueStats(C.Structure):
     _fields_ = [("anchors", C.c_uint64), ("capped_queries", C.c_uint64), ("starts", C.c_uint64),
                 ("rescued", C.c_uint64), ("batches", C.c_uint64), ("kernel_ms", C.c_double)]
@@ -130,6 +140,9 @@ EXPORTED = {
     "sahara_gpu_loci_stats": (C.c_int, [C.c_void_p, C.POINTER(LociStats)]),
     "sahara_gpu_set_pairs": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32]),
     "sahara_gpu_pairs_stats": (C.c_int, [C.c_void_p, C.POINTER(PairsStats)]),
+    "sahara_gpu_set_best_pairs": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
+    "sahara_gpu_pair_summary": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "sahara_gpu_best_pairs_stats": (C.c_int, [C.c_void_p, C.POINTER(BestPairsStats)]),
     "sahara_gpu_set_rescue": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32]),
     "sahara_gpu_rescue_stats": (C.c_int, [C.c_void_p, C.POINTER(RescueStats)]),
     "sahara_gpu_select_part": (C.c_int, [C.c_void_p, C.c_uint32]),
@@ -386,6 +399,37 @@ class BiFMIndex:
         s = PairsStats()
         _check(lib().sahara_gpu_pairs_stats(self._h, C.byref(s)))
         return {n: getattr(s, n) for n, _ in s._fields_}
+
+    def set_best_pairs(self, delta):
+        """Best pairs (docs/semantics.md "Best pairs"), for calls with pairs on:
+        with an int in [0, 30], the pair stage keeps of each read pair only
+        its least-error concordant placements: the hits whose errors plus
+        their cheapest mate's are within `delta` of the pair's best total,
+        each position once. set_best_pairs(None) turns it off. The setting
+        stays until changed."""
+        if delta is None:
+            _check(lib().sahara_gpu_set_best_pairs(self._h, 0, 0))
+            return
+        if not 0 <= int(delta) <= 0xFFFFFFFF:
+            raise ValueError("delta must be in [0, 2^32)")
+        _check(lib().sahara_gpu_set_best_pairs(self._h, 1, int(delta)))
+
+    def best_pairs_stats(self):
+        """Figures of the pair stage's best mode in the last search call (zeros if it was off)."""
+        s = BestPairsStats()
+        _check(lib().sahara_gpu_best_pairs_stats(self._h, C.byref(s)))
+        return {n: getattr(s, n) for n, _ in s._fields_}
+
+    def pair_summary(self):
+        """The last search call's per-pair records (PAIR_SUMMARY_DTYPE, pair p
+        of the call at index p): best and next totals (PAIR_NONE: none), the
+        kept hits of the pair's even and odd qids. Refused if that call ran
+        without best pairs."""
+        n = C.c_uint64(0)
+        _check(lib().sahara_gpu_pair_summary(self._h, None, 0, C.byref(n)))  # (the count alone)
+        out = np.zeros(n.value, PAIR_SUMMARY_DTYPE)
+        _check(lib().sahara_gpu_pair_summary(self._h, out.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
+        return out
 
     def set_rescue(self, max_err, max_anchors=64):
         """Mate rescue (docs/semantics.md "Mate rescue"), for calls with pairs

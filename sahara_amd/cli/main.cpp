@@ -452,9 +452,13 @@ int cmdSearch(int argc, char** argv) {
     // mate rescue (docs/semantics.md "Mate rescue"): a hit without a mate gets its fragment window scanned for the
     // partner read with up to n errors; --rescue-anchors a: a read with more than a such hits is left alone (0: no cap)
     Opt rescue{{"--rescue"}}, rescueAnchors{{"--rescue-anchors"}, false, "64"};
+    // best pairs (docs/semantics.md "Best pairs"): of the concordant placements of a pair only those within
+    // --pair-delta errors of its best; --pair-summary <file>: a line per pair that keeps a hit
+    Opt bestPairs{{"--best-pairs"}, true}, pairDelta{{"--pair-delta"}, false, "0"}, pairSummary{{"--pair-summary"}};
     Parser p;
     for (Opt* o : {&query, &index, &output, &gen, &dyn, &errors, &noRev, &mode, &dist, &maxHits, &limit, &gpus,
-                   &emitErr, &fmOnly, &emitCigar, &loci, &lociWindow, &paired, &minFrag, &maxFrag, &rescue, &rescueAnchors})
+                   &emitErr, &fmOnly, &emitCigar, &loci, &lociWindow, &paired, &minFrag, &maxFrag, &rescue, &rescueAnchors,
+                   &bestPairs, &pairDelta, &pairSummary})
         p.add(*o);
     p.parse(argc, argv, 2);
     if (!p.positional.empty()) throw CliError("unexpected argument " + p.positional[0]);
@@ -491,6 +495,12 @@ int cmdSearch(int argc, char** argv) {
             throw CliError("--rescue takes 1 to " + std::to_string(SAHARA_ALIGN_MAX_ERR) + " errors");
         if (rescueA > 0xFFFFFFFFull) throw CliError("--rescue-anchors is at most 4294967295");
     }
+    if ((pairDelta.given || pairSummary.given) && !bestPairs.given)
+        throw CliError("--pair-delta / --pair-summary need --best-pairs");
+    if (bestPairs.given && !paired.given) throw CliError("--best-pairs needs --paired (the placements ranked are pairs')");
+    const uint64_t bestDelta = toU64(pairDelta.value, "--pair-delta");
+    if (bestDelta > SAHARA_BEST_PAIRS_MAX_DELTA)
+        throw CliError("--pair-delta is at most " + std::to_string(SAHARA_BEST_PAIRS_MAX_DELTA));
     // (a rescued hit carries up to --rescue errors: --emit-cigar aligns with the larger bound)
     const uint32_t alignK = (uint32_t)std::max<uint64_t>((uint64_t)k, rescueK);
 
@@ -615,6 +625,8 @@ int cmdSearch(int argc, char** argv) {
         for (void* c : ctx) check(sahara_gpu_set_pairs(c, 1, (uint32_t)fragLo, (uint32_t)fragHi), "set pairs");
     if (rescue.given)  // (a window lies on the anchor's record, and a pair in one shard)
         for (void* c : ctx) check(sahara_gpu_set_rescue(c, 1, (uint32_t)rescueK, (uint32_t)rescueA), "set rescue");
+    if (bestPairs.given)  // (a pair lies in one shard)
+        for (void* c : ctx) check(sahara_gpu_set_best_pairs(c, 1, (uint32_t)bestDelta), "set best pairs");
     sahara_index_info info{};
     check(sahara_gpu_index_info(ctx[0], &info), "index info");
     timing.emplace_back("ld index", sw.reset());
@@ -709,6 +721,9 @@ int cmdSearch(int argc, char** argv) {
     std::vector<sahara_loci_stats> devLoci(ngpu);
     std::vector<sahara_pairs_stats> devPairs(ngpu);
     std::vector<sahara_rescue_stats> devRescue(ngpu);
+    std::vector<sahara_best_pairs_stats> devBest(ngpu);
+    std::vector<std::vector<sahara_pair_summary>> devSummary(ngpu);  // per shard: its pairs', the first being pair q0 / 4
+    std::vector<uint64_t> devPair0(ngpu, 0);
     {
         std::vector<std::thread> th;
         for (uint32_t g = 0; g < ngpu; ++g) {
@@ -760,6 +775,19 @@ int cmdSearch(int argc, char** argv) {
                 if (lociOn) sahara_gpu_loci_stats(ctx[g], &devLoci[g]);
                 if (paired.given) sahara_gpu_pairs_stats(ctx[g], &devPairs[g]);
                 if (rescue.given) sahara_gpu_rescue_stats(ctx[g], &devRescue[g]);
+                if (bestPairs.given) {
+                    sahara_gpu_best_pairs_stats(ctx[g], &devBest[g]);
+                    if (pairSummary.given) {
+                        uint64_t np = 0;
+                        devSummary[g].resize((q1 - q0) / 4);
+                        devPair0[g] = q0 / 4;
+                        if (sahara_gpu_pair_summary(ctx[g], devSummary[g].data(), devSummary[g].size(), &np) != 0 ||
+                            np != devSummary[g].size()) {
+                            errs[g] = std::string("pair summary: ") + sahara_gpu_last_error();
+                            return;
+                        }
+                    }
+                }
                 devSearch[g] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
                 part.hits = hits;
                 part.n = nh;
@@ -809,6 +837,18 @@ int cmdSearch(int argc, char** argv) {
     for (auto& hp : parts) nhits += hp.n;
     writeHits(output.value, parts, emitErr.given, nt, emitCigar.given ? len : 0);
     for (auto& hp : parts) hp.release();
+    if (pairSummary.given) {  // the shards' summaries in shard order, the pair numbers the call's
+        FILE* f = std::fopen(pairSummary.value.c_str(), "w");
+        if (!f) throw CliError("cannot write " + pairSummary.value);
+        for (uint32_t g = 0; g < ngpu; ++g)
+            for (size_t i = 0; i < devSummary[g].size(); ++i) {
+                const sahara_pair_summary& x = devSummary[g][i];
+                if (x.best != 255)
+                    std::fprintf(f, "%llu\t%u\t%u\t%u\t%u\n", (unsigned long long)(devPair0[g] + i), x.best, x.next,
+                                 x.n_fwd, x.n_rev);
+            }
+        if (std::fclose(f) != 0) throw CliError("cannot write " + pairSummary.value);
+    }
     timing.emplace_back("result", sw.reset());
     for (void*& c : ctx) {
         sahara_gpu_close(c);
@@ -833,6 +873,12 @@ int cmdSearch(int argc, char** argv) {
         unsigned long long in = 0, kept = 0, np = 0;
         for (const sahara_pairs_stats& s : devPairs) in += s.hits_in, kept += s.kept, np += s.pairs;
         std::printf("  pairs:               %llu of %llu hits, %llu pairs\n", kept, in, np);
+    }
+    if (bestPairs.given) {
+        unsigned long long in = 0, kept = 0, np = 0, uniq = 0;
+        for (const sahara_best_pairs_stats& s : devBest) in += s.hits_in, kept += s.kept, np += s.pairs, uniq += s.unique_pairs;
+        std::printf("  best pairs:          %llu of %llu hits, %llu pairs, %llu unique (delta %llu)\n", kept, in, np, uniq,
+                    (unsigned long long)bestDelta);
     }
     if (rescue.given) {
         unsigned long long anchors = 0, starts = 0, found = 0, capped = 0;
@@ -891,6 +937,9 @@ void help() {
         "                [--rescue <n>] [--rescue-anchors <a>]   with --paired: a hit without a mate gets its\n"
         "                fragment window scanned for the other read with up to n errors (1..8); a read with\n"
         "                more than a such hits is left alone (64; 0: no cap)\n"
+        "                [--best-pairs] [--pair-delta <d>] [--pair-summary <file>]   with --paired: of a pair's\n"
+        "                concordant placements only those within d errors (0; at most 30) of its best, each\n"
+        "                position once; the file gets pair, best, next, n_fwd, n_rev per pair that keeps a hit\n"
         "  sahara read_simulator -o <fasta> [-i <reference>] [-l <len>] [-n <reads>] [-e <errors>]\n"
         "                [--substitution_errors n] [--insertion_errors n] [--deletion_errors n]\n"
         "                [--fasta_line_length n] [--seed s]\n"

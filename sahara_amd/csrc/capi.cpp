@@ -258,7 +258,7 @@ ReadRows readRows(int reverse, uint64_t n_reads, uint64_t limit) {
 // The pair stage's refusals of a reads or packed call, before anything is staged (docs/semantics.md
 // "Pairs"): the mates' reverse complements are what pairs with them, and the list holds whole pairs.
 static void checkPairsReads(const Ctx* c, int reverse, const ReadRows& R, uint32_t len) {
-    if (!c->pairs.on) return;
+    if (!c->pairs.on) return checkPairsCall(c, R.npat, len);  // (what needs pairs on is refused there)
     if (!reverse) throw Error("pairs: a reads call needs reverse != 0 (a mate pairs with its partner's reverse complement)");
     checkPairsCall(c, R.npat, len);
 }

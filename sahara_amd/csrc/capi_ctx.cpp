@@ -367,6 +367,51 @@ int sahara_gpu_pairs_stats(void* ctx, sahara_pairs_stats* stats) {
     });
 }
 
+int sahara_gpu_set_best_pairs(void* ctx, int on, uint32_t delta) {
+    return guarded([&] {
+        if (on && delta > SAHARA_BEST_PAIRS_MAX_DELTA)
+            throw Error("sahara_gpu_set_best_pairs: delta must be in [0, " + std::to_string(SAHARA_BEST_PAIRS_MAX_DELTA) +
+                        "]");
+        Ctx* c = ctxOf(ctx);
+        c->pairs.best = on != 0;
+        c->pairs.delta = on ? delta : 0u;
+    });
+}
+
+int sahara_gpu_pair_summary(void* ctx, sahara_pair_summary* out, uint64_t capacity, uint64_t* n_pairs) {
+    return guarded([&] {
+        Ctx* c = ctxOf(ctx);
+        if (!c->pairs.summaryOn) throw Error("sahara_gpu_pair_summary: the last search call ran without best pairs");
+        if (n_pairs) *n_pairs = c->pairs.summaryPairs;
+        if (!out && capacity == 0) return;  // the count alone
+        if (capacity < c->pairs.summaryPairs) throw Error("sahara_gpu_pair_summary: capacity too small");
+        if (c->pairs.summaryPairs && !out) throw Error("sahara_gpu_pair_summary: null output");
+        std::copy_n(c->pairs.summary.ptr, c->pairs.summaryPairs, out);
+    });
+}
+
+// (the pairs are counted from the summary, so an overflow re-run leaves the figures of the batches that count)
+int sahara_gpu_best_pairs_stats(void* ctx, sahara_best_pairs_stats* stats) {
+    return guarded([&] {
+        if (!stats) throw Error("sahara_gpu_best_pairs_stats: null output");
+        const Ctx* c = ctxOf(ctx);
+        sahara_best_pairs_stats s{};
+        if (c->pairs.summaryOn) {
+            const sahara_pairs_stats& p = c->stageStats.pairs;
+            s.hits_in = p.hits_in;
+            s.kept = p.kept;
+            s.batches = p.batches;
+            s.kernel_ms = p.kernel_ms;
+            for (uint64_t i = 0; i < c->pairs.summaryPairs; ++i) {
+                const sahara_pair_summary& x = c->pairs.summary.ptr[i];
+                s.pairs += x.best != 255;
+                s.unique_pairs += x.n_fwd == 1 && x.n_rev == 1;
+            }
+        }
+        *stats = s;
+    });
+}
+
 int sahara_gpu_set_rescue(void* ctx, int on, uint32_t max_err, uint32_t max_anchors) {
     return guarded([&] {
         if (on && (max_err < 1 || max_err > SAHARA_ALIGN_MAX_ERR))

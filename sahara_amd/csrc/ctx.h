@@ -363,6 +363,15 @@ struct Ctx {
         bool on = false;
         uint32_t minFrag = 0, maxFrag = 0;
         PairsBufs bufs;
+        // Best mode (docs/semantics.md "Best pairs"; sahara_gpu_set_best_pairs):
+        // the stage keeps each pair's least-error placements within delta.
+        // summary: the last call's per-pair records in pinned host memory,
+        // sized per call (pass.cpp run); summaryOn: that call ran in best mode.
+        bool best = false;
+        uint32_t delta = 0;
+        PinnedBuf<sahara_pair_summary> summary;
+        uint64_t summaryPairs = 0;
+        bool summaryOn = false;
     } pairs;
     // The mate rescue (docs/semantics.md "Mate rescue"; rescue.hip): a setting
     // of the context too (sahara_gpu_set_rescue), which needs the pair stage

@@ -11,12 +11,15 @@
 //
 // A pair's four qids lie in one batch (pass_plan.h, granularity 4), so the
 // partner's records are all here. The rule's pieces are pairs_core.h's.
+// In best mode (docs/semantics.md "Best pairs") four more kernels cut the
+// flags down to each pair's least-error placements before the scan and write
+// a summary per pair after it: see "best mode" below.
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
-#include "pairs_core.h"
+#include "best_pairs_core.h"
 #include "search_device.h"
 
 namespace sahara {
@@ -102,6 +105,162 @@ __global__ __launch_bounds__(256) void kPairGather(const sahara_hit* __restrict_
     if (lane == 0 && counted) atomicAdd(pairs, (unsigned long long)counted);
 }
 
+// ---- best mode (docs/semantics.md "Best pairs"): between
+// kPairFlags and the scan, the flags are cut down to each pair's least-error
+// placements, and after the scan one lane per pair writes the pair's summary.
+//
+//   kBestBlocks   err of record i as a byte; its least over each aligned block of 64  -> err8[i], blk[i / 64]
+//   kBestScore    record i with a mate: its mates' index range (two lower bounds), the
+//                 least err in it (bestRangeMin), m[i] = the sum; atomicMin into best[pair]
+//   kBestFlags    flag[i] = first of its position && m[i] <= best[pair] + delta;
+//                 atomicMin of the other first-of-position scores into next[pair]
+//   kBestSummary  (after the scan) per pair: best, next, the kept records of its even
+//                 and odd qids from num at its segments' ends                          -> sum[pair]
+//
+// The per-record kernels walk the records a wave at a time, as loci.hip's do:
+// every lane runs every iteration, only loads, stores and atomics are predicated.
+
+struct ErrAt {
+    const uint8_t* e;
+    __device__ __forceinline__ uint32_t operator()(uint64_t i) const { return e[i]; }
+};
+
+// The minimum of `key` over each run of lanes with equal `run` (runs do not
+// decrease from lane to lane: the records are sorted by qid), left in the
+// run's last lane: the segmented min-scan of kLociReduce. A tandem run puts
+// thousands of records on one pair: one atomic per run and wave, not per record.
+struct RunMin {
+    uint32_t key;
+    bool last;
+};
+__device__ __forceinline__ RunMin runMin(uint32_t key, uint32_t run, uint32_t lane) {
+    const uint32_t below = __shfl_up(run, 1);
+    const uint64_t firsts = __ballot(lane == 0 || below != run);
+    const uint32_t first = 63u - (uint32_t)__clzll((long long)(firsts & (~0ull >> (63u - lane))));
+#pragma unroll
+    for (uint32_t off = 1; off < 64; off <<= 1) {
+        const uint32_t o = __shfl_up(key, off);
+        if (lane >= first + off) key = o < key ? o : key;
+    }
+    return {key, lane == 63u || ((firsts >> (lane + 1u)) & 1ull) != 0};
+}
+
+__global__ __launch_bounds__(256) void kBestBlocks(const sahara_hit* __restrict__ h, uint64_t n,
+                                                   uint8_t* __restrict__ err8, uint8_t* __restrict__ blk) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x - lane); base < n; base += stride) {
+        const uint64_t i = base + lane;
+        uint32_t e = kBestNone;
+        if (i < n) {
+            e = min(h[i].err, kBestNone - 1u);
+            err8[i] = (uint8_t)e;
+        }
+#pragma unroll
+        for (uint32_t off = 32; off; off >>= 1) e = min(e, (uint32_t)__shfl_xor(e, (int)off));
+        if (lane == 0) blk[base / kBestBlock] = (uint8_t)e;  // (base is a multiple of 64)
+    }
+}
+
+__global__ __launch_bounds__(256) void kBestScore(const sahara_hit* __restrict__ h, uint64_t n, uint64_t dmin,
+                                                  uint64_t dmax, const uint64_t* __restrict__ qoff, uint64_t qidBase,
+                                                  uint32_t nq, const uint32_t* __restrict__ flag,
+                                                  const uint8_t* __restrict__ err8, const uint8_t* __restrict__ blk,
+                                                  uint8_t* __restrict__ m, uint32_t* __restrict__ best) {
+    const HitAt at{h};
+    const ErrAt errAt{err8}, blockAt{blk};
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x - lane); base < n; base += stride) {
+        const uint64_t i = base + lane;
+        const bool valid = i < n;
+        uint32_t score = kBestNone, pair = 0xFFFFFFFFu;
+        if (valid) {
+            const sahara_hit x = h[i];
+            const uint64_t q = x.qid - qidBase;
+            if (q < nq) pair = (uint32_t)(q >> 2);
+            const uint64_t p = pairPartner(x.qid) - qidBase;
+            if (flag[i] != 0 && p < nq) {  // (a mate lies in the partner's segment: kPairFlags found it there)
+                const uint64_t last = min(qoff[p + 1], n), first = min(qoff[p], last);
+                const BestRange r = bestMateRange(at, x.qid, x.seq_id, x.pos, dmin, dmax, first, last);
+                score = bestScore(min(x.err, kBestNone - 1u), bestRangeMin(errAt, blockAt, r.lb, r.ub));
+            }
+            m[i] = (uint8_t)min(score, kBestNone);
+        }
+        const RunMin r = runMin(score, pair, lane);
+        if (r.last && r.key < kBestNone && pair != 0xFFFFFFFFu) atomicMin(best + pair, r.key);
+    }
+}
+
+// The neighbour's fields come from the lane below; lane 0 reads record i - 1 itself (kLociHeads).
+__global__ __launch_bounds__(256) void kBestFlags(const sahara_hit* __restrict__ h, uint64_t n, uint64_t qidBase,
+                                                  uint32_t nq, uint32_t delta, const uint8_t* __restrict__ m,
+                                                  const uint32_t* __restrict__ best, uint32_t* __restrict__ next,
+                                                  uint32_t* __restrict__ flag) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x - lane); base < n; base += stride) {
+        const uint64_t i = base + lane;
+        const bool valid = i < n;
+        sahara_hit x{};
+        if (valid) x = h[i];
+        uint64_t pq = __shfl_up(x.qid, 1);
+        uint32_t ps = __shfl_up(x.seq_id, 1);
+        uint64_t pp = __shfl_up(x.pos, 1);
+        if (lane == 0 && valid && i > 0) {
+            const sahara_hit p = h[i - 1];
+            pq = p.qid;
+            ps = p.seq_id;
+            pp = p.pos;
+        }
+        uint32_t pair = 0xFFFFFFFFu, other = kBestNone;
+        if (valid) {
+            const bool firstOfPos = i == 0 || pq != x.qid || ps != x.seq_id || pp != x.pos;
+            const uint64_t q = x.qid - qidBase;
+            const uint32_t score = m[i];
+            bool keep = false;
+            if (q < nq && score != kBestNone) {  // (then best[pair] has a value: at most this score)
+                pair = (uint32_t)(q >> 2);
+                const uint32_t b = best[pair];
+                keep = bestKeeps(firstOfPos, score, b, delta);
+                if (firstOfPos && score > b) other = score;
+            } else if (q < nq) {
+                pair = (uint32_t)(q >> 2);
+            }
+            flag[i] = keep ? 1u : 0u;
+        }
+        const RunMin r = runMin(other, pair, lane);
+        if (r.last && r.key < kBestNone && pair != 0xFFFFFFFFu) atomicMin(next + pair, r.key);
+    }
+}
+
+// One lane per pair, no atomics: the kept records of query q are num's growth
+// over its segment [qoff[q], qoff[q + 1]), the flags' inclusive sum at the
+// segment's ends (the segments of the records the flags were made for). The
+// grid holds every pair (a batch has fewer than 2^30: the launch has no cap
+// and the kernel no loop).
+__global__ __launch_bounds__(256) void kBestSummary(const uint32_t* __restrict__ num, uint64_t n,
+                                                    const uint64_t* __restrict__ qoff, uint32_t npairs,
+                                                    const uint32_t* __restrict__ best,
+                                                    const uint32_t* __restrict__ next,
+                                                    sahara_pair_summary* __restrict__ sum) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= npairs) return;
+    uint32_t cnt[2] = {0, 0};
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) {
+        const uint64_t e = min(qoff[4 * (uint64_t)p + k + 1], n), b = min(qoff[4 * (uint64_t)p + k], e);
+        cnt[k & 1u] += (e ? num[e - 1] : 0u) - (b ? num[b - 1] : 0u);
+    }
+    sahara_pair_summary s;
+    s.best = (uint8_t)min(best[p], kBestNone);
+    s.next = (uint8_t)min(next[p], kBestNone);
+    s.n_fwd = (uint16_t)min(cnt[0], 65535u);
+    s.n_rev = (uint16_t)min(cnt[1], 65535u);
+    s.reserved = 0;
+    sum[p] = s;
+}
+
 }  // namespace
 
 // flag[i] = record i of the batch has a concordant mate in it (kPairFlags): the pair stage's first
@@ -119,21 +278,51 @@ void launchPairFlags(const BatchView& v, uint64_t dmin, uint64_t dmax, uint32_t*
 // call is refused otherwise, capi.cpp). Host-synchronous like lociBatch: the
 // kept count sizes the rest of the batch's chain. The number of pairs that
 // keep a hit arrives in *hostPairs (pinned) once v.st has passed this call's
-// last copy: the caller reads it after the batch's chain.
-void pairsBatch(BatchView& v, uint32_t len, uint32_t minFrag, uint32_t maxFrag, PairsBufs& B, uint64_t* hostPairs) {
+// last copy: the caller reads it after the batch's chain. best != nullptr:
+// best mode, which keeps of those hits each pair's least-error placements
+// (within best->delta) and copies the batch's pair summaries to
+// best->summary[q0 / 4 ..] (pinned, read after the batch's chain as well).
+void pairsBatch(BatchView& v, uint32_t len, uint32_t minFrag, uint32_t maxFrag, PairsBufs& B, uint64_t* hostPairs,
+                const BestPairsIn* best) {
     *hostPairs = 0;
     const uint64_t rows = v.rows;
     if (rows == 0) return;
     if (rows >= (1ull << 32)) throw Error("more than 2^32 hits in one batch of patterns");  // (the 32-bit running count)
     if (maxFrag < len) throw Error("pairs: max_fragment is below the pattern length (internal)");
+    if (best && (v.nq % 4 || v.q0 % 4)) throw Error("best pairs: a batch is not cut at whole pairs (internal)");
     room(B.flag, rows);
     room(B.num, rows);
     B.pairs.reserve(1);
     const PairDist d = pairDist(len, minFrag, maxFrag);
     const uint32_t blocks = (uint32_t)std::min<uint64_t>((rows + 255) / 256, 8192);
     launchPairFlags(v, d.dmin, d.dmax, B.flag.ptr);
+    const uint32_t npairs = v.nq / 4;
+    if (best) {  // the flags cut down to the least-error placements; best[] and next[] start as "no value"
+        room(B.err8, rows);
+        room(B.score, rows);
+        room(B.blk, (rows + kBestBlock - 1) / kBestBlock);
+        room(B.best, 2 * (uint64_t)npairs);
+        room(B.sum, npairs);
+        uint32_t* const next = B.best.ptr + npairs;
+        SH_HIP(hipMemsetAsync(B.best.ptr, 0xFF, 2 * (size_t)npairs * sizeof(uint32_t), v.st));
+        hipLaunchKernelGGL(kBestBlocks, dim3(blocks), dim3(256), 0, v.st, v.hits, rows, B.err8.ptr, B.blk.ptr);
+        SH_HIP(hipGetLastError());
+        hipLaunchKernelGGL(kBestScore, dim3(blocks), dim3(256), 0, v.st, v.hits, rows, d.dmin, d.dmax, v.qoff, v.q0, v.nq,
+                           B.flag.ptr, B.err8.ptr, B.blk.ptr, B.score.ptr, B.best.ptr);
+        SH_HIP(hipGetLastError());
+        hipLaunchKernelGGL(kBestFlags, dim3(blocks), dim3(256), 0, v.st, v.hits, rows, v.q0, v.nq, best->delta,
+                           B.score.ptr, B.best.ptr, next, B.flag.ptr);
+        SH_HIP(hipGetLastError());
+    }
     const uint64_t kept = scanFlagsCount(B.flag.ptr, B.num.ptr, v);
     if (kept > rows) throw Error("pairs: the kept count is out of range (internal)");
+    if (best) {  // before replaceBatch writes the segments again: the counts are taken at the old ones
+        hipLaunchKernelGGL(kBestSummary, dim3((npairs + 255) / 256), dim3(256), 0, v.st, B.num.ptr, rows, v.qoff, npairs, B.best.ptr,
+                           B.best.ptr + npairs, B.sum.ptr);
+        SH_HIP(hipGetLastError());
+        SH_HIP(hipMemcpyAsync(best->summary + v.q0 / 4, B.sum.ptr, (size_t)npairs * sizeof(sahara_pair_summary),
+                              hipMemcpyDeviceToHost, v.st));
+    }
     if (kept == 0) {  // (no rows: no later stage runs on them, nothing reads the segments)
         v.rows = 0;
         return;

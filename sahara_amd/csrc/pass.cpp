@@ -13,6 +13,7 @@
 
 #include "ctx.h"
 #include "align_core.h"
+#include "best_pairs_core.h"
 #include "rescue_core.h"
 
 namespace sahara {
@@ -42,6 +43,9 @@ DeviceIndex& partOf(Ctx* c, uint32_t p) { return p == 0 ? c->I : c->more.at(p - 
 // the anchor's record and a record lies wholly in one part, whose text and
 // record starts the scan reads; an anchor of the merged hits is an anchor of
 // its part's hits, since its mates could only lie on its own record.
+// Best pairs on a multi-part index: refused. A pair's best total is a minimum
+// over all its placements, and the cut per part would keep in each part what
+// is best there, not what is best over all parts.
 void checkPairsCall(const Ctx* c, uint64_t npat, uint32_t len) {
     if (c->rescue.on) {  // (docs/semantics.md "Mate rescue", refused calls)
         if (!c->pairs.on) throw Error("rescue: needs pairs on (a mate is looked for in the pair rule's fragment window)");
@@ -53,6 +57,12 @@ void checkPairsCall(const Ctx* c, uint64_t npat, uint32_t len) {
                 throw Error("rescue: the fragment window of " + std::to_string(d.dmax - d.dmin + 1) +
                             " starts is above SAHARA_RESCUE_MAX_WINDOW (" + std::to_string(kRescueMaxWindow) + ")");
         }
+    }
+    if (c->pairs.best) {  // (docs/semantics.md "Best pairs", refused calls)
+        if (!c->pairs.on) throw Error("best pairs: needs pairs on (the placements ranked are the pair rule's)");
+        if (!c->more.empty())
+            throw Error("best pairs: a multi-part index is not supported (a pair's best total over one part is not "
+                        "its best over all parts)");
     }
     if (!c->pairs.on) return;
     if (c->pairs.maxFrag < len)
@@ -66,6 +76,11 @@ void checkPairsCall(const Ctx* c, uint64_t npat, uint32_t len) {
 void run(Ctx* c, bool count) {
     c->stageStats = Ctx::StageStats{};  // of this call: the passes below add to them
     if (c->sk.staged) checkPairsCall(c, c->npat, c->m);
+    // best pairs: the call's pair summaries, one per four patterns (runPass fills them with "keeps nothing",
+    // the batches' pair stages write over that); a call with the mode off leaves none behind
+    c->pairs.summaryOn = c->sk.staged && c->pairs.on && c->pairs.best;
+    c->pairs.summaryPairs = c->pairs.summaryOn ? c->npat / 4 : 0;
+    if (c->pairs.summaryOn) c->pairs.summary.reserve(std::max<uint64_t>(c->pairs.summaryPairs, 1));
     if (c->more.empty()) return runOne(c, count);
     // (rounds mask a query by its rows in one part; "found" is decided across the parts: capi.cpp bestOnHost)
     if (c->rounds.size() > 1) throw Error("a pass of several rounds needs a single-part index");
@@ -761,11 +776,17 @@ struct Pass {
                 rescueMerge(v, r, c->rescue.bufs);
                 break;
             }
-            case kStagePairs:  // docs/semantics.md "Pairs": the hits with a mate in the batch, which holds whole pairs
+            case kStagePairs: {
+                // docs/semantics.md "Pairs": the hits with a mate in the batch, which holds whole pairs; in
+                // best mode ("Best pairs") of those each pair's least-error placements, and `kept` counts
+                // what leaves the stage either way
+                const BestPairsIn best{c->pairs.delta, c->pairs.summary.ptr};
                 T.pairs.hits_in += v.rows;
-                pairsBatch(v, c->m, c->pairs.minFrag, c->pairs.maxFrag, c->pairs.bufs, &rec.pairs);
+                pairsBatch(v, c->m, c->pairs.minFrag, c->pairs.maxFrag, c->pairs.bufs, &rec.pairs,
+                           c->pairs.summaryOn ? &best : nullptr);
                 T.pairs.kept += v.rows;
                 break;
+            }
             case kStageLimit:  // --max_hits: this batch's queries keep their n best positions (search_n)
                 limitBatch(v, c->sk.limitN, c->limit);
                 break;
@@ -928,6 +949,8 @@ void runPass(Ctx* c, bool count, bool redo, sahara_stats& S, bool& overflow) {
     c->mark("pass", 0);
     syncAll({c->st, c->stB, c->stC, c->stD});
     c->mark("pass synced", 0);
+    if (c->pairs.summaryOn)  // (a re-run after an overflow starts from the same: no copy of the first pass is in flight)
+        std::fill_n(c->pairs.summary.ptr, c->pairs.summaryPairs, sahara_pair_summary{kBestNone, kBestNone, 0, 0, 0});
     if (count) {
         SH_HIP(hipMemsetAsync(c->counters.ptr, 0, kCounters * sizeof(unsigned long long), ps.sA));
         for (Counter minimum : {kCtBornMin, kCtEndMin, kCtDryMin})

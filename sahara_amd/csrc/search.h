@@ -336,9 +336,20 @@ void rescueMerge(BatchView& v, uint64_t r, RescueBufs& B);
 struct PairsBufs {
     DevBuf<uint32_t> flag, num;         // per record: has a mate; the flags' inclusive sum
     DevBuf<unsigned long long> pairs;   // one word: the pairs that keep a hit
+    // best mode (docs/semantics.md "Best pairs"):
+    DevBuf<uint8_t> err8, blk, score;   // per record: its err; per aligned 64 records: their least err; per record: m
+    DevBuf<uint32_t> best;              // per pair of the batch: s1, then (a second array behind it) next
+    DevBuf<sahara_pair_summary> sum;    // per pair of the batch: its summary, copied to the host per batch
 };
-// *hostPairs (pinned) gets the pairs with a kept hit once v.st has passed the call
-void pairsBatch(BatchView& v, uint32_t len, uint32_t minFrag, uint32_t maxFrag, PairsBufs& B, uint64_t* hostPairs);
+// best mode of the pair stage: the slack, and the call's pair summaries in pinned host memory (pair 0 of the
+// call first; a batch writes its pairs' from q0 / 4 on)
+struct BestPairsIn {
+    uint32_t delta;
+    sahara_pair_summary* summary;
+};
+// *hostPairs (pinned) gets the pairs with a kept hit once v.st has passed the call; best: nullptr = off
+void pairsBatch(BatchView& v, uint32_t len, uint32_t minFrag, uint32_t maxFrag, PairsBufs& B, uint64_t* hostPairs,
+                const BestPairsIn* best);
 // flag[i] = record i of the batch has a concordant mate in it, searched for within the partner query's
 // segment (the pair stage's first step, and the rescue's)
 void launchPairFlags(const BatchView& v, uint64_t dmin, uint64_t dmax, uint32_t* flag);
