@@ -409,6 +409,54 @@ typedef struct sahara_best_pairs_stats {   /* 48 B */
 /* ... of the context's last search call; zeros if best pairs were off. */
 int  sahara_gpu_best_pairs_stats(void* ctx, sahara_best_pairs_stats* stats);
 
+/* --- pair links (docs/semantics.md "Pair links") ---
+ * With best pairs on, the stage knows for every hit it keeps which hit goes
+ * with it, which placement of the pair is the one to report and how far the
+ * next one lies. With pair links on as well it writes that down, on the
+ * device, one 8-byte record per hit of the call's output (hit i of `hits`, of
+ * a compact call's records or of sahara_gpu_fetch has link i):
+ *   mate   the index of the hit's least-error concordant mate (ties: the
+ *          smaller position) among the call's hits, minus the hit's own index.
+ *          The mate is a kept hit of the same pair.
+ *   score  m(i): the hit's errors plus that mate's.
+ *   flags  bit 0 (SAHARA_LINK_PRIMARY): the hit is one of the pair's two
+ *          primary records: the kept hit of an even qid with the least
+ *          (score, index), and its mate. Their score is the pair's best and
+ *          their links point at each other; the links of secondary hits need
+ *          not be mutual.
+ *   mapq   on primary records the pair's MAPQ (sahara_pair_mapq); else 0.
+ * on != 0: every later search call of this context writes links; on == 0 (the
+ * default) restores the calls as they were. With links on a search call is
+ * refused before any device work if best pairs are off or if it has max_hits
+ * > 0 (the cut would drop linked hits). The hits of the call are unchanged. */
+#define SAHARA_LINK_PRIMARY 1u
+typedef struct sahara_pair_link {      /* 8 B */
+    int32_t mate;      /* index of the mate among the call's hits minus this hit's own index */
+    uint8_t score;     /* m(i) */
+    uint8_t mapq;
+    uint8_t flags;     /* bit 0: primary */
+    uint8_t reserved;  /* 0 */
+} sahara_pair_link;
+int  sahara_gpu_set_pair_links(void* ctx, int on);
+/* The last search call's links into out[0 .. *n_links), one per hit of that
+ * call. out == NULL with capacity == 0 asks for the count alone. Refused if
+ * that call ran without links, if capacity is below the count or if out is
+ * NULL with a capacity. */
+int  sahara_gpu_pair_links(void* ctx, sahara_pair_link* out, uint64_t capacity, uint64_t* n_links);
+/* A pair's MAPQ, a policy of this build (host only, no context): n_best is
+ * the larger of the pair's kept even-qid and kept odd-qid hits whose score is
+ * s->best. n_best >= 3: 0; 2: 1; 1: 10 * min(s->next - s->best, 6), 60 where
+ * the pair has no next. 0 for a pair that keeps nothing (or s == NULL). */
+uint32_t sahara_pair_mapq(const sahara_pair_summary* s, uint32_t n_best);
+typedef struct sahara_pair_links_stats {   /* 24 B */
+    uint64_t links;      /* links written: the call's hits */
+    uint64_t primaries;  /* ... of them primary: two per pair that keeps a hit */
+    double   kernel_ms;  /* device time of the two link kernels (HIP events), summed over batches;
+                            it is part of the pair stage's kernel_ms */
+} sahara_pair_links_stats;
+/* ... of the context's last search call; zeros if links were off. */
+int  sahara_gpu_pair_links_stats(void* ctx, sahara_pair_links_stats* stats);
+
 /* --- mate rescue (docs/semantics.md "Mate rescue") ---
  * With pairs on, a hit whose partner query has no hit in its fragment window
  * is dropped, even where the partner lies there with a few errors more than

@@ -23,7 +23,7 @@ __all__ = [
     "BiFMIndex", "HIT_DTYPE", "search", "search_reads", "search_reads_compact", "CompactHits", "PackedReads",
     "pack_reads", "search_packed", "search_packed_compact", "search_best", "search_best_reads", "search_best_packed",
     "search_best_packed_compact", "ALIGN_DTYPE", "ALIGN_MAX_ERR", "ALIGN_NONE", "align", "align_packed_compact",
-    "align_stats", "cigar", "PAIR_SUMMARY_DTYPE", "PAIR_NONE", "read_fasta", "search_scheme", "scheme_parts",
+    "align_stats", "cigar", "PAIR_SUMMARY_DTYPE", "PAIR_NONE", "PAIR_LINK_DTYPE", "LINK_PRIMARY", "pair_mapq", "read_fasta", "search_scheme", "scheme_parts",
     "scheme_generators",
     "scheme_counts", "synth_reference", "synth_reads", "interleave_rc", "load_fasta",
     "library_path", "lib", "SaharaError", "DNA5", "DNA4",
@@ -114,6 +114,13 @@ class BestPairsStats(C.Structure):
 # sahara_pair_summary (include/sahara_hip.h): one record per pair of a call with best pairs on
 PAIR_SUMMARY_DTYPE = np.dtype([("best", "u1"), ("next", "u1"), ("n_fwd", "<u2"), ("n_rev", "<u2"), ("reserved", "<u2")])
 PAIR_NONE = 255
+# sahara_pair_link (include/sahara_hip.h): one record per hit of a call with pair links on
+PAIR_LINK_DTYPE = np.dtype([("mate", "<i4"), ("score", "u1"), ("mapq", "u1"), ("flags", "u1"), ("reserved", "u1")])
+LINK_PRIMARY = 1
+
+
+class PairLinksStats(C.Structure):
+    _fields_ = [("links", C.c_uint64), ("primaries", C.c_uint64), ("kernel_ms", C.c_double)]
 
 
 class RescueStats(C.Structure):
@@ -143,6 +150,10 @@ EXPORTED = {
     "sahara_gpu_set_best_pairs": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
     "sahara_gpu_pair_summary": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "sahara_gpu_best_pairs_stats": (C.c_int, [C.c_void_p, C.POINTER(BestPairsStats)]),
+    "sahara_gpu_set_pair_links": (C.c_int, [C.c_void_p, C.c_int]),
+    "sahara_gpu_pair_links": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "sahara_pair_mapq": (C.c_uint32, [C.c_void_p, C.c_uint32]),
+    "sahara_gpu_pair_links_stats": (C.c_int, [C.c_void_p, C.POINTER(PairLinksStats)]),
     "sahara_gpu_set_rescue": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32]),
     "sahara_gpu_rescue_stats": (C.c_int, [C.c_void_p, C.POINTER(RescueStats)]),
     "sahara_gpu_select_part": (C.c_int, [C.c_void_p, C.c_uint32]),
@@ -430,6 +441,32 @@ class BiFMIndex:
         out = np.zeros(n.value, PAIR_SUMMARY_DTYPE)
         _check(lib().sahara_gpu_pair_summary(self._h, out.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
         return out
+
+    def set_pair_links(self, on):
+        """Pair links (docs/semantics.md "Pair links"), for calls with best
+        pairs on: with a true value, every later search call also writes one
+        link per hit it returns (pair_links()): the hit's mate, its pair
+        score, whether it is one of the pair's two primary records, and on
+        those the pair's MAPQ. A call with max_hits is then refused.
+        set_pair_links(False) or (None) turns it off. The setting stays until
+        changed; the hits of a call do not depend on it."""
+        _check(lib().sahara_gpu_set_pair_links(self._h, 1 if on else 0))
+
+    def pair_links(self):
+        """The last search call's links (PAIR_LINK_DTYPE), link i for hit i of
+        what the call returned: `mate` is the mate's index minus i. Refused if
+        that call ran without pair links."""
+        n = C.c_uint64(0)
+        _check(lib().sahara_gpu_pair_links(self._h, None, 0, C.byref(n)))  # (the count alone)
+        out = np.zeros(n.value, PAIR_LINK_DTYPE)
+        _check(lib().sahara_gpu_pair_links(self._h, out.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
+        return out
+
+    def pair_links_stats(self):
+        """Figures of the links in the last search call (zeros if they were off)."""
+        s = PairLinksStats()
+        _check(lib().sahara_gpu_pair_links_stats(self._h, C.byref(s)))
+        return {n: getattr(s, n) for n, _ in s._fields_}
 
     def set_rescue(self, max_err, max_anchors=64):
         """Mate rescue (docs/semantics.md "Mate rescue"), for calls with pairs
@@ -798,6 +835,15 @@ def cigar(record, length):
     buf = C.create_string_buffer(cap)
     n = lib().sahara_cigar(r.ctypes.data_as(C.c_void_p), int(length), buf, cap)
     return buf.raw[:n].decode() if n >= 0 else None
+
+
+def pair_mapq(best, next, n_best):
+    """A pair's MAPQ from its summary's best and next totals and n_best, the
+    larger of its kept even-qid and kept odd-qid hits whose score is `best`
+    (sahara_pair_mapq; docs/semantics.md "Pair links"). Host only."""
+    s = np.zeros(1, PAIR_SUMMARY_DTYPE)
+    s["best"], s["next"] = best, next
+    return int(lib().sahara_pair_mapq(s.ctypes.data_as(C.c_void_p), int(n_best)))
 
 
 def read_fasta(path, sigma=6, form=1, threads=0):

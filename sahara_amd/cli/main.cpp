@@ -207,6 +207,7 @@ struct HitPart {
     uint64_t n = 0;
     uint64_t qidOffset = 0;
     std::vector<sahara_alignment> aln;  // --emit-cigar: record i of hit i, aligned by the hit's own device
+    std::vector<sahara_pair_link> links;  // --sam: link i of hit i, relative within the shard
     void release() {
         if (compact) sahara_gpu_free_blocks(&blocks);
         else sahara_gpu_free(hits);
@@ -215,17 +216,14 @@ struct HitPart {
     }
 };
 
-// Text output of hits: "qid seqId pos[ e][ cigar]\n" (search.cpp:254-261; the
-// CIGAR of patterns of cigarLen symbols when the parts carry alignments). Blocks of
-// hits are formatted by nt threads, each taking the next block in order; a
-// block's file offset is the previous block's end, published as soon as that
-// block is formatted, so each thread writes its own block (pwrite) while the
-// others format theirs: formatting and writing both run on every thread.
-// Compact records are decoded right here, in the formatting loop that runs
-// anyway: record id by the record starts (usually the previous hit's record),
-// position, errors.
-void writeHits(const std::string& path, const std::vector<HitPart>& parts, bool emitErrors, unsigned nt,
-               uint32_t cigarLen = 0) {
+// The parallel writer: nblocks blocks of text, formatted by nt threads, each
+// taking the next block in order (format(bi, buf) fills buf and returns the
+// bytes it used). A block's file offset is the previous block's end,
+// published as soon as that block is formatted, so each thread writes its own
+// block (pwrite) while the others format theirs: formatting and writing both
+// run on every thread.
+template <typename Format>
+void writeBlocks(const std::string& path, size_t nblocks, unsigned nt, Format&& format) {
     const int fd = ::open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
     if (fd < 0) throw CliError("can not open output file " + path);
     struct CloseFd {  // closed on every path out (formatting may throw, e.g. bad_alloc)
@@ -234,15 +232,7 @@ void writeHits(const std::string& path, const std::vector<HitPart>& parts, bool 
         int close() { closed = true; return ::close(fd); }
         ~CloseFd() { if (!closed) (void)::close(fd); }
     } closer{fd};
-    struct Block {
-        const HitPart* part;
-        uint64_t lo, hi;
-    };
-    std::vector<Block> blocks;
-    constexpr uint64_t kBlock = 1u << 18;  // hits per block (~7 MB of text)
-    for (const auto& hp : parts)
-        for (uint64_t lo = 0; lo < hp.n; lo += kBlock) blocks.push_back({&hp, lo, std::min(hp.n, lo + kBlock)});
-    std::vector<std::atomic<int64_t>> ends(blocks.size());
+    std::vector<std::atomic<int64_t>> ends(nblocks);
     for (auto& e : ends) e.store(-1, std::memory_order_relaxed);
     std::atomic<size_t> next{0};
     std::atomic<bool> failed{false};
@@ -250,67 +240,17 @@ void writeHits(const std::string& path, const std::vector<HitPart>& parts, bool 
         std::vector<char> buf;
         for (;;) {
             const size_t bi = next.fetch_add(1, std::memory_order_relaxed);
-            if (bi >= blocks.size()) return;
+            if (bi >= nblocks) return;
             // A block that fails to format still publishes its end (as an
             // empty block), so that the blocks after it do not wait forever;
             // the call then fails.
-            auto publishEmpty = [&] {
-                int64_t off = 0;
-                if (bi > 0)
-                    while ((off = ends[bi - 1].load(std::memory_order_acquire)) < 0) std::this_thread::yield();
-                ends[bi].store(off, std::memory_order_release);
-            };
-            const Block& B = blocks[bi];
+            int64_t size = 0;
             try {
-                buf.resize((B.hi - B.lo) * (cigarLen ? 256 : 96));
+                size = (int64_t)format(bi, buf);
             } catch (...) {
                 failed.store(true);
-                publishEmpty();
-                continue;
+                size = 0;
             }
-            char* o = buf.data();
-            char* e = o + buf.size();
-            const HitPart& P = *B.part;
-            auto line = [&](uint64_t k, uint64_t qid, uint64_t seq, uint64_t pos, uint32_t err) {
-                o = std::to_chars(o, e, qid).ptr;
-                *o++ = ' ';
-                o = std::to_chars(o, e, seq).ptr;
-                *o++ = ' ';
-                o = std::to_chars(o, e, pos).ptr;
-                if (emitErrors) {
-                    *o++ = ' ';
-                    o = std::to_chars(o, e, err).ptr;
-                }
-                if (cigarLen) {  // (at most 8 edits: < 150 characters)
-                    *o++ = ' ';
-                    const int n = sahara_cigar(&P.aln[k], cigarLen, o, (size_t)(e - o));
-                    if (n >= 0) o += n;
-                    else *o++ = '*';  // no alignment within the bound
-                }
-                *o++ = '\n';
-            };
-            if (!P.compact) {
-                for (uint64_t k = B.lo; k < B.hi; ++k) {
-                    const sahara_hit& h = P.hits[k];
-                    line(k, h.qid + P.qidOffset, h.seq_id, h.pos, h.err);
-                }
-            } else {
-                const sahara_hit_blocks& H = P.blocks;
-                const uint64_t* S = H.rec_starts;
-                uint64_t blk = (uint64_t)(std::upper_bound(H.block_end, H.block_end + H.n_blocks, B.lo) - H.block_end);
-                uint64_t seq = 0, lo = 1, hi = 0;  // the current record's [start, next start): empty
-                for (uint64_t k = B.lo; k < B.hi; ++k) {
-                    while (k >= H.block_end[blk]) ++blk;
-                    const uint64_t v = H.recs[k], g = (v >> 4) & 0xFFFFFFFFull;
-                    if (g < lo || g >= hi) {
-                        seq = (uint64_t)(std::upper_bound(S, S + H.n_records + 1, g) - S) - 1;
-                        lo = S[seq];
-                        hi = S[seq + 1];
-                    }
-                    line(k, H.block_qid0[blk] + (v >> 36) + P.qidOffset, seq, g - lo, (uint32_t)(v & 15u));
-                }
-            }
-            const int64_t size = (int64_t)(o - buf.data());
             int64_t off = 0;
             if (bi > 0)
                 while ((off = ends[bi - 1].load(std::memory_order_acquire)) < 0) std::this_thread::yield();
@@ -323,6 +263,235 @@ void writeHits(const std::string& path, const std::vector<HitPart>& parts, bool 
         }
     });
     if (closer.close() != 0 || failed.load()) throw CliError("can not write output file " + path);
+}
+
+// Text output of hits: "qid seqId pos[ e][ cigar]\n" (search.cpp:254-261; the
+// CIGAR of patterns of cigarLen symbols when the parts carry alignments), in
+// blocks of hits through writeBlocks. Compact records are decoded right here,
+// in the formatting loop that runs anyway: record id by the record starts
+// (usually the previous hit's record), position, errors.
+void writeHits(const std::string& path, const std::vector<HitPart>& parts, bool emitErrors, unsigned nt,
+               uint32_t cigarLen = 0) {
+    struct Block {
+        const HitPart* part;
+        uint64_t lo, hi;
+    };
+    std::vector<Block> blocks;
+    constexpr uint64_t kBlock = 1u << 18;  // hits per block (~7 MB of text)
+    for (const auto& hp : parts)
+        for (uint64_t lo = 0; lo < hp.n; lo += kBlock) blocks.push_back({&hp, lo, std::min(hp.n, lo + kBlock)});
+    writeBlocks(path, blocks.size(), nt, [&](size_t bi, std::vector<char>& buf) {
+        const Block& B = blocks[bi];
+        buf.resize((B.hi - B.lo) * (cigarLen ? 256 : 96));
+        char* o = buf.data();
+        char* e = o + buf.size();
+        const HitPart& P = *B.part;
+        auto line = [&](uint64_t k, uint64_t qid, uint64_t seq, uint64_t pos, uint32_t err) {
+            o = std::to_chars(o, e, qid).ptr;
+            *o++ = ' ';
+            o = std::to_chars(o, e, seq).ptr;
+            *o++ = ' ';
+            o = std::to_chars(o, e, pos).ptr;
+            if (emitErrors) {
+                *o++ = ' ';
+                o = std::to_chars(o, e, err).ptr;
+            }
+            if (cigarLen) {  // (at most 8 edits: < 150 characters)
+                *o++ = ' ';
+                const int n = sahara_cigar(&P.aln[k], cigarLen, o, (size_t)(e - o));
+                if (n >= 0) o += n;
+                else *o++ = '*';  // no alignment within the bound
+            }
+            *o++ = '\n';
+        };
+        if (!P.compact) {
+            for (uint64_t k = B.lo; k < B.hi; ++k) {
+                const sahara_hit& h = P.hits[k];
+                line(k, h.qid + P.qidOffset, h.seq_id, h.pos, h.err);
+            }
+        } else {
+            const sahara_hit_blocks& H = P.blocks;
+            const uint64_t* S = H.rec_starts;
+            uint64_t blk = (uint64_t)(std::upper_bound(H.block_end, H.block_end + H.n_blocks, B.lo) - H.block_end);
+            uint64_t seq = 0, lo = 1, hi = 0;  // the current record's [start, next start): empty
+            for (uint64_t k = B.lo; k < B.hi; ++k) {
+                while (k >= H.block_end[blk]) ++blk;
+                const uint64_t v = H.recs[k], g = (v >> 4) & 0xFFFFFFFFull;
+                if (g < lo || g >= hi) {
+                    seq = (uint64_t)(std::upper_bound(S, S + H.n_records + 1, g) - S) - 1;
+                    lo = S[seq];
+                    hi = S[seq + 1];
+                }
+                line(k, H.block_qid0[blk] + (v >> 36) + P.qidOffset, seq, g - lo, (uint32_t)(v & 15u));
+            }
+        }
+        return (size_t)(o - buf.data());
+    });
+}
+
+// --sam (docs/semantics.md "SAM output"): the kept hits of a --best-pairs
+// search as SAM records, a line per hit, from the shards' hits (compact
+// records), links and alignments; a pair that keeps nothing writes its two
+// reads unmapped. Names are numbers: QNAME the pair, RNAME the record. The
+// pairs are written in query order in blocks through writeBlocks; block 0 is
+// the header.
+struct SamReads {
+    const uint8_t* codes;  // two bits per symbol, A C G T = 0 1 2 3, read r at symbol r * len
+    const uint64_t* npos;  // the positions that hold an N, ascending
+    uint64_t ncount;
+    uint32_t len;
+    // the pattern of qid (read qid / 2; odd: its reverse complement) in letters
+    void pattern(uint64_t qid, char* out) const {
+        const uint64_t s0 = (qid >> 1) * len;
+        for (uint32_t j = 0; j < len; ++j) out[j] = "ACGT"[(codes[(s0 + j) >> 2] >> (2 * ((s0 + j) & 3))) & 3];
+        const uint64_t* b = npos ? std::lower_bound(npos, npos + ncount, s0) : nullptr;
+        for (; b && b < npos + ncount && *b < s0 + len; ++b) out[*b - s0] = 'N';
+        if (qid & 1) {
+            std::reverse(out, out + len);
+            for (uint32_t j = 0; j < len; ++j)
+                out[j] = out[j] == 'A' ? 'T' : out[j] == 'C' ? 'G' : out[j] == 'G' ? 'C' : out[j] == 'T' ? 'A' : 'N';
+        }
+    }
+};
+
+void writeSam(const std::string& path, const std::vector<HitPart>& parts, const SamReads& R, uint64_t npairs,
+              unsigned nt) {
+    const sahara_hit_blocks* any = nullptr;
+    for (const auto& hp : parts)
+        if (hp.compact) any = &hp.blocks;
+    if (!any) throw CliError("--sam: no shard returned compact records");
+    // the shards' hits as whole records (qids of the call), decoded in parallel
+    std::vector<std::vector<sahara_hit>> whole(parts.size());
+    for (size_t g = 0; g < parts.size(); ++g) {
+        const HitPart& P = parts[g];
+        if (!P.n) continue;
+        if (!P.compact || P.links.size() != P.n || P.aln.size() != P.n)
+            throw CliError("--sam: a shard's hits came without links or alignments");
+        whole[g].resize(P.n);
+        const sahara_hit_blocks& H = P.blocks;
+        parallelFor(nt, nt, [&](size_t t) {
+            const uint64_t a = P.n * t / nt, b = P.n * (t + 1) / nt;
+            if (a == b) return;
+            uint64_t blk = (uint64_t)(std::upper_bound(H.block_end, H.block_end + H.n_blocks, a) - H.block_end);
+            for (uint64_t k = a; k < b; ++k) {
+                while (k >= H.block_end[blk]) ++blk;
+                const uint64_t v = H.recs[k], gpos = (v >> 4) & 0xFFFFFFFFull;
+                const uint64_t seq = (uint64_t)(std::upper_bound(H.rec_starts, H.rec_starts + H.n_records + 1, gpos) -
+                                                H.rec_starts) - 1;
+                whole[g][k] = {H.block_qid0[blk] + (v >> 36) + P.qidOffset, (uint32_t)seq, (uint32_t)(v & 15u),
+                               gpos - H.rec_starts[seq]};
+            }
+        });
+    }
+    struct Block {
+        size_t part;      // the shard that holds the pairs (parts.size(): none of them has a hit there)
+        uint64_t p0, p1;  // pairs [p0, p1)
+    };
+    // the pairs in blocks, cut at the shards' borders: shard g holds the pairs from its qidOffset / 4 up to the next's
+    std::vector<Block> blocks;
+    constexpr uint64_t kBlock = 1u << 14;  // pairs per block (>= 2 lines each)
+    {
+        uint64_t p = 0;
+        auto add = [&](size_t part, uint64_t upTo) {
+            for (; p < upTo; p += std::min(kBlock, upTo - p)) blocks.push_back({part, p, std::min(upTo, p + kBlock)});
+        };
+        for (size_t g = 0; g < parts.size(); ++g) {
+            if (!parts[g].n) continue;
+            add(parts.size(), parts[g].qidOffset / 4);  // (pairs before this shard's first: of shards without a hit)
+            uint64_t end = npairs;
+            for (size_t h = g + 1; h < parts.size(); ++h)
+                if (parts[h].n) {
+                    end = parts[h].qidOffset / 4;
+                    break;
+                }
+            add(g, end);
+        }
+        add(parts.size(), npairs);
+    }
+    const uint32_t len = R.len;
+    writeBlocks(path, blocks.size() + 1, nt, [&](size_t bi, std::vector<char>& buf) {
+        buf.clear();
+        auto text = [&](const char* s) { buf.insert(buf.end(), s, s + std::strlen(s)); };
+        auto num = [&](long long v) {
+            char b[24];
+            const auto r = std::to_chars(b, b + sizeof(b), v);
+            buf.insert(buf.end(), b, r.ptr);
+        };
+        if (bi == 0) {
+            text("@HD\tVN:1.6\tSO:unsorted\tGO:query\n");
+            for (uint64_t r = 0; r < any->n_records; ++r) {
+                text("@SQ\tSN:");
+                num((long long)r);
+                text("\tLN:");
+                num((long long)(any->rec_starts[r + 1] - any->rec_starts[r] - 1));
+                text("\n");
+            }
+            text("@PG\tID:sahara\tPN:sahara\n");
+            return buf.size();
+        }
+        const Block& B = blocks[bi - 1];
+        std::vector<char> seq(len);
+        auto pattern = [&](uint64_t qid) {
+            R.pattern(qid, seq.data());
+            buf.insert(buf.end(), seq.begin(), seq.end());
+        };
+        const std::vector<sahara_hit>* W = B.part < parts.size() ? &whole[B.part] : nullptr;
+        uint64_t k = 0;
+        if (W) k = (uint64_t)(std::lower_bound(W->begin(), W->end(), 4 * B.p0,
+                                               [](const sahara_hit& h, uint64_t q) { return h.qid < q; }) - W->begin());
+        for (uint64_t p = B.p0; p < B.p1; ++p) {
+            if (!W || k >= W->size() || (*W)[k].qid >> 2 != p) {  // the pair keeps nothing: its two reads, unmapped
+                for (int mate = 0; mate < 2; ++mate) {
+                    num((long long)p);
+                    text(mate ? "\t141\t*\t0\t0\t*\t*\t0\t0\t" : "\t77\t*\t0\t0\t*\t*\t0\t0\t");
+                    pattern(4 * p + 2 * mate);
+                    text("\t*\n");
+                }
+                continue;
+            }
+            const HitPart& P = parts[B.part];
+            for (; k < W->size() && (*W)[k].qid >> 2 == p; ++k) {
+                const sahara_hit& h = (*W)[k];
+                const sahara_pair_link& L = P.links[k];
+                const uint64_t km = (uint64_t)((int64_t)k + L.mate);
+                if (km >= W->size()) throw CliError("--sam: a link leaves its shard's hits");
+                const sahara_hit& m = (*W)[km];
+                const sahara_alignment &A = P.aln[k], &Am = P.aln[km];
+                const bool none = A.err == SAHARA_ALIGN_NONE, noneM = Am.err == SAHARA_ALIGN_NONE;
+                const uint64_t end = h.pos + (none ? len : A.ref_len), endM = m.pos + (noneM ? len : Am.ref_len);
+                const long long span = (long long)(std::max(end, endM) - std::min(h.pos, m.pos));
+                const bool left = h.pos < m.pos || (h.pos == m.pos && (h.qid & 1) == 0);
+                const unsigned flag = 0x1u | 0x2u | ((h.qid & 1) ? 0x10u : 0x20u) | ((h.qid & 2) ? 0x80u : 0x40u) |
+                                      ((L.flags & SAHARA_LINK_PRIMARY) ? 0u : 0x100u);
+                num((long long)p);
+                text("\t");
+                num(flag);
+                text("\t");
+                num(h.seq_id);
+                text("\t");
+                num((long long)h.pos + 1);
+                text("\t");
+                num(L.mapq);
+                text("\t");
+                char cg[16 * (SAHARA_ALIGN_MAX_ERR + 2)];
+                const int n = sahara_cigar(&A, len, cg, sizeof(cg));
+                if (n >= 0) buf.insert(buf.end(), cg, cg + n);
+                else text("*");  // no alignment within the bound
+                text("\t=\t");
+                num((long long)m.pos + 1);
+                text("\t");
+                num(left ? span : -span);
+                text("\t");
+                pattern(h.qid);
+                text("\t*\tNM:i:");
+                num(none ? (long long)h.err : (long long)A.err);
+                text("\tZP:i:");
+                num(L.score);
+                text("\n");
+            }
+        }
+        return buf.size();
+    });
 }
 
 // A read-only mapping of a whole file (the .idx image every device loads).
@@ -455,10 +624,13 @@ int cmdSearch(int argc, char** argv) {
     // best pairs (docs/semantics.md "Best pairs"): of the concordant placements of a pair only those within
     // --pair-delta errors of its best; --pair-summary <file>: a line per pair that keeps a hit
     Opt bestPairs{{"--best-pairs"}, true}, pairDelta{{"--pair-delta"}, false, "0"}, pairSummary{{"--pair-summary"}};
+    // SAM output (docs/semantics.md "SAM output"): with --paired --best-pairs, -o becomes a SAM file of the kept
+    // hits with their mates, MAPQ and CIGAR (pair links and the alignment call)
+    Opt sam{{"--sam"}, true};
     Parser p;
     for (Opt* o : {&query, &index, &output, &gen, &dyn, &errors, &noRev, &mode, &dist, &maxHits, &limit, &gpus,
                    &emitErr, &fmOnly, &emitCigar, &loci, &lociWindow, &paired, &minFrag, &maxFrag, &rescue, &rescueAnchors,
-                   &bestPairs, &pairDelta, &pairSummary})
+                   &bestPairs, &pairDelta, &pairSummary, &sam})
         p.add(*o);
     p.parse(argc, argv, 2);
     if (!p.positional.empty()) throw CliError("unexpected argument " + p.positional[0]);
@@ -484,8 +656,16 @@ int cmdSearch(int argc, char** argv) {
             throw CliError("--paired: --limit_queries must be a multiple of 4 (a pair is two mates and their reverse "
                            "complements)");
     }
-    if (emitCigar.given && k > SAHARA_ALIGN_MAX_ERR)
-        throw CliError("--emit-cigar aligns at most " + std::to_string(SAHARA_ALIGN_MAX_ERR) + " errors (-e)");
+    if (sam.given) {
+        if (!paired.given || !bestPairs.given)
+            throw CliError("--sam needs --paired --best-pairs (a SAM record names its mate, and a pair's primary "
+                           "placement and MAPQ come from the best-pairs rule)");
+        if (mh > 0) throw CliError("--sam cannot go with --max_hits (the cut would drop linked hits)");
+    }
+    const bool align = emitCigar.given || sam.given;  // --sam implies the alignment call of --emit-cigar
+    if (align && k > SAHARA_ALIGN_MAX_ERR)
+        throw CliError(std::string(sam.given ? "--sam" : "--emit-cigar") + " aligns at most " +
+                       std::to_string(SAHARA_ALIGN_MAX_ERR) + " errors (-e)");
     if (rescueAnchors.given && !rescue.given) throw CliError("--rescue-anchors needs --rescue");
     const uint64_t rescueK = rescue.given ? toU64(rescue.value, "--rescue") : 0;
     const uint64_t rescueA = toU64(rescueAnchors.value, "--rescue-anchors");
@@ -627,6 +807,8 @@ int cmdSearch(int argc, char** argv) {
         for (void* c : ctx) check(sahara_gpu_set_rescue(c, 1, (uint32_t)rescueK, (uint32_t)rescueA), "set rescue");
     if (bestPairs.given)  // (a pair lies in one shard)
         for (void* c : ctx) check(sahara_gpu_set_best_pairs(c, 1, (uint32_t)bestDelta), "set best pairs");
+    if (sam.given)  // (a link is an offset within its pair's hits, which lie in one shard)
+        for (void* c : ctx) check(sahara_gpu_set_pair_links(c, 1), "set pair links");
     sahara_index_info info{};
     check(sahara_gpu_index_info(ctx[0], &info), "index info");
     timing.emplace_back("ld index", sw.reset());
@@ -703,7 +885,10 @@ int cmdSearch(int argc, char** argv) {
     // hits as compact records where they apply (no --max_hits, one index
     // part, <= 15 errors; SAHARA_CLI_FULL_HITS=1: whole records)
     const char* fullEnv = std::getenv("SAHARA_CLI_FULL_HITS");
-    const bool compactOut = mh <= 0 && info.n_parts == 1 && k <= 15 && !(fullEnv && std::atoi(fullEnv));
+    // (--sam: always compact records, which carry the record starts that the header and the positions need; its
+    // other conditions hold: no --max_hits, at most 8 errors, and best pairs refuse a multi-part index)
+    const bool compactOut = mh <= 0 && info.n_parts == 1 && k <= 15 && (sam.given || !(fullEnv && std::atoi(fullEnv)));
+    if (sam.given && !compactOut) throw CliError("--sam needs a single-part index");
     // besthits: the exact-j schemes back to back (sahara_gpu_search_best's form)
     std::vector<uint32_t> bestPi, bestL, bestU, bestNs;
     if (besthits)
@@ -724,6 +909,7 @@ int cmdSearch(int argc, char** argv) {
     std::vector<sahara_best_pairs_stats> devBest(ngpu);
     std::vector<std::vector<sahara_pair_summary>> devSummary(ngpu);  // per shard: its pairs', the first being pair q0 / 4
     std::vector<uint64_t> devPair0(ngpu, 0);
+    std::vector<sahara_pair_links_stats> devLinks(ngpu);
     {
         std::vector<std::thread> th;
         for (uint32_t g = 0; g < ngpu; ++g) {
@@ -788,13 +974,23 @@ int cmdSearch(int argc, char** argv) {
                         }
                     }
                 }
+                if (sam.given) {
+                    uint64_t nl = 0;
+                    part.links.resize(nh);
+                    if (sahara_gpu_pair_links(ctx[g], part.links.data(), nh, &nl) != 0 || nl != nh) {
+                        errs[g] = std::string("pair links: ") + sahara_gpu_last_error();
+                        part.release();
+                        return;
+                    }
+                    sahara_gpu_pair_links_stats(ctx[g], &devLinks[g]);
+                }
                 devSearch[g] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
                 part.hits = hits;
                 part.n = nh;
                 part.qidOffset = q0;
                 // --emit-cigar: the shard's hits aligned on its own device, before the merge. besthits
                 // searches with edit operations whatever -d says, so its hits align with them too
-                if (emitCigar.given && nh) {
+                if (align && nh) {
                     const auto tA = std::chrono::steady_clock::now();
                     const int alignEdit = edit || besthits ? 1 : 0;
                     try {
@@ -831,11 +1027,19 @@ int cmdSearch(int argc, char** argv) {
     const double aln = *std::max_element(devAlign.begin(), devAlign.end());
     timing.emplace_back("search", std::max(0.0, wall - loc - aln));
     timing.emplace_back("locate", loc);
-    if (emitCigar.given) timing.emplace_back("align", aln);
+    if (align) timing.emplace_back("align", aln);
 
     uint64_t nhits = 0;
     for (auto& hp : parts) nhits += hp.n;
-    writeHits(output.value, parts, emitErr.given, nt, emitCigar.given ? len : 0);
+    unsigned long long mapq30 = 0;  // --sam: the pairs whose primary records carry a MAPQ of 30 or more
+    if (sam.given) {
+        for (const auto& hp : parts)
+            for (const sahara_pair_link& l : hp.links) mapq30 += (l.flags & SAHARA_LINK_PRIMARY) && l.mapq >= 30;
+        mapq30 /= 2;  // (two primary records per pair)
+        writeSam(output.value, parts, SamReads{reads, Q.f.n_count ? Q.f.n_pos : nullptr, Q.f.n_count, len}, nq / 4, nt);
+    } else {
+        writeHits(output.value, parts, emitErr.given, nt, emitCigar.given ? len : 0);
+    }
     for (auto& hp : parts) hp.release();
     if (pairSummary.given) {  // the shards' summaries in shard order, the pair numbers the call's
         FILE* f = std::fopen(pairSummary.value.c_str(), "w");
@@ -879,6 +1083,11 @@ int cmdSearch(int argc, char** argv) {
         for (const sahara_best_pairs_stats& s : devBest) in += s.hits_in, kept += s.kept, np += s.pairs, uniq += s.unique_pairs;
         std::printf("  best pairs:          %llu of %llu hits, %llu pairs, %llu unique (delta %llu)\n", kept, in, np, uniq,
                     (unsigned long long)bestDelta);
+    }
+    if (sam.given) {
+        unsigned long long links = 0, prim = 0;
+        for (const sahara_pair_links_stats& s : devLinks) links += s.links, prim += s.primaries;
+        std::printf("  pair links:          %llu links, %llu primary, %llu pairs with MAPQ >= 30\n", links, prim, mapq30);
     }
     if (rescue.given) {
         unsigned long long anchors = 0, starts = 0, found = 0, capped = 0;
@@ -940,6 +1149,8 @@ void help() {
         "                [--best-pairs] [--pair-delta <d>] [--pair-summary <file>]   with --paired: of a pair's\n"
         "                concordant placements only those within d errors (0; at most 30) of its best, each\n"
         "                position once; the file gets pair, best, next, n_fwd, n_rev per pair that keeps a hit\n"
+        "                [--sam]   with --paired --best-pairs: -o becomes a SAM file, a record per kept hit with\n"
+        "                its mate, MAPQ and CIGAR; a pair that keeps nothing writes its reads unmapped\n"
         "  sahara read_simulator -o <fasta> [-i <reference>] [-l <len>] [-n <reads>] [-e <errors>]\n"
         "                [--substitution_errors n] [--insertion_errors n] [--deletion_errors n]\n"
         "                [--fasta_line_length n] [--seed s]\n"

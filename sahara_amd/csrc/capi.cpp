@@ -517,6 +517,8 @@ static void streamedCall(Ctx* c, const Queries& q, const Schemes& sc, Out& out) 
 
 static void searchWhole(Ctx* c, const Queries& q, const Schemes& sc, uint32_t max_hits, sahara_hit** hits,
                         uint64_t* n_hits) {
+    if (max_hits && c->pairs.links)  // (docs/semantics.md "Pair links", refused calls)
+        throw Error("pair links: a call with max_hits is not supported (the cut would drop linked hits)");
     WholeHits out{max_hits, hits, n_hits};
     streamedCall(c, q, sc, out);
 }
@@ -543,6 +545,7 @@ static void searchBlocks(Ctx* c, const uint8_t* reads, uint64_t n_reads, uint32_
 // streamed pass (pass.cpp).
 static void bestOnHost(Ctx* c, const uint8_t* ranks, uint64_t n_patterns, uint32_t len, const Schemes& sc,
                        uint32_t max_hits, sahara_hit** hits, uint64_t* n_hits) {
+    if (c->pairs.links) throw Error("pair links: besthits on the host is not supported (its hits are merged on the host)");
     std::vector<uint64_t> todo(n_patterns);
     for (uint64_t i = 0; i < n_patterns; ++i) todo[i] = i;
     std::vector<uint8_t> sub;

@@ -16,6 +16,7 @@
 
 #include "ctx.h"
 #include "idx_format.h"
+#include "pair_links_core.h"
 
 using namespace sahara;
 
@@ -407,6 +408,41 @@ int sahara_gpu_best_pairs_stats(void* ctx, sahara_best_pairs_stats* stats) {
                 s.pairs += x.best != 255;
                 s.unique_pairs += x.n_fwd == 1 && x.n_rev == 1;
             }
+        }
+        *stats = s;
+    });
+}
+
+int sahara_gpu_set_pair_links(void* ctx, int on) {
+    return guarded([&] { ctxOf(ctx)->pairs.links = on != 0; });
+}
+
+int sahara_gpu_pair_links(void* ctx, sahara_pair_link* out, uint64_t capacity, uint64_t* n_links) {
+    return guarded([&] {
+        Ctx* c = ctxOf(ctx);
+        if (!c->pairs.linksOn) throw Error("sahara_gpu_pair_links: the last search call ran without pair links");
+        if (n_links) *n_links = c->pairs.linkCount;
+        if (!out && capacity == 0) return;  // the count alone
+        if (capacity < c->pairs.linkCount) throw Error("sahara_gpu_pair_links: capacity too small");
+        if (c->pairs.linkCount && !out) throw Error("sahara_gpu_pair_links: null output");
+        std::copy_n(c->pairs.linkBuf.ptr, c->pairs.linkCount, out);
+    });
+}
+
+uint32_t sahara_pair_mapq(const sahara_pair_summary* s, uint32_t n_best) {
+    return s ? pairMapq(s->best, s->next, n_best) : 0u;
+}
+
+// (links and primaries are counted from the links, so an overflow re-run leaves the figures of the batches that count)
+int sahara_gpu_pair_links_stats(void* ctx, sahara_pair_links_stats* stats) {
+    return guarded([&] {
+        if (!stats) throw Error("sahara_gpu_pair_links_stats: null output");
+        const Ctx* c = ctxOf(ctx);
+        sahara_pair_links_stats s{};
+        if (c->pairs.linksOn) {
+            s.links = c->pairs.linkCount;
+            s.kernel_ms = c->stageStats.linkMs;
+            for (uint64_t i = 0; i < c->pairs.linkCount; ++i) s.primaries += c->pairs.linkBuf.ptr[i].flags & kLinkPrimary;
         }
         *stats = s;
     });

@@ -334,6 +334,7 @@ struct Ctx {
         sahara_loci_stats loci{};
         sahara_rescue_stats rescue{};
         sahara_pairs_stats pairs{};
+        double linkMs = 0;  // the pair stage's two link kernels, a part of pairs.kernel_ms
         // by Stage, what every stage keeps alike: the batches it ran on and its
         // HIP-event time (--max_hits keeps no figures: nulls)
         struct Figures {
@@ -372,6 +373,14 @@ struct Ctx {
         PinnedBuf<sahara_pair_summary> summary;
         uint64_t summaryPairs = 0;
         bool summaryOn = false;
+        // Links (docs/semantics.md "Pair links"; sahara_gpu_set_pair_links):
+        // in best mode the stage also writes one link per hit it keeps.
+        // linkBuf: the last call's, in pinned host memory, hit 0 first, grown
+        // per batch; linksOn: that call wrote them, linkCount of them.
+        bool links = false;
+        PinnedBuf<sahara_pair_link> linkBuf;
+        uint64_t linkCount = 0;
+        bool linksOn = false;
     } pairs;
     // The mate rescue (docs/semantics.md "Mate rescue"; rescue.hip): a setting
     // of the context too (sahara_gpu_set_rescue), which needs the pair stage

@@ -13,13 +13,16 @@
 // partner's records are all here. The rule's pieces are pairs_core.h's.
 // In best mode (docs/semantics.md "Best pairs") four more kernels cut the
 // flags down to each pair's least-error placements before the scan and write
-// a summary per pair after it: see "best mode" below.
+// a summary per pair after it: see "best mode" below. With links on
+// (docs/semantics.md "Pair links") two more write a link per kept record
+// before the gather: see "links" below.
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
 #include "best_pairs_core.h"
+#include "pair_links_core.h"
 #include "search_device.h"
 
 namespace sahara {
@@ -261,6 +264,123 @@ __global__ __launch_bounds__(256) void kBestSummary(const uint32_t* __restrict__
     sum[p] = s;
 }
 
+// ---- links (docs/semantics.md "Pair links"): after the scan
+// and the summary, before the gather, every kept record gets a link.
+//
+//   kLinkMates  kept record i: its mate range again and the first record in it with the
+//               least err (bestRangeArgMin)                                  -> mate[i];
+//               atomicMin of (m, i) over the kept even-qid records           -> key[pair];
+//               the kept records with m == s1, even and odd qids apart       -> ties[2 pair], ties[2 pair + 1]
+//   kLinkWrite  kept record i -> link[num[i] - 1]: the mate's offset among the kept records,
+//               m, primary (i is the key's record, or that record's mate), the pair's MAPQ
+//
+// The atomics are per run and wave, as kBestScore's: a tandem run puts hundreds
+// of kept records on one pair.
+
+// The lanes at which a run of equal `run` starts and ends, for the segmented scans below (runMin's)
+struct RunEnds {
+    uint32_t first;  // the first lane of this lane's run
+    bool last;       // this lane is its run's last
+};
+__device__ __forceinline__ RunEnds runEnds(uint32_t run, uint32_t lane) {
+    const uint32_t below = __shfl_up(run, 1);
+    const uint64_t firsts = __ballot(lane == 0 || below != run);
+    const uint32_t first = 63u - (uint32_t)__clzll((long long)(firsts & (~0ull >> (63u - lane))));
+    return {first, lane == 63u || ((firsts >> (lane + 1u)) & 1ull) != 0};
+}
+
+__global__ __launch_bounds__(256) void kLinkMates(const sahara_hit* __restrict__ h, uint64_t n, uint64_t dmin,
+                                                  uint64_t dmax, const uint64_t* __restrict__ qoff, uint64_t qidBase,
+                                                  uint32_t nq, const uint32_t* __restrict__ flag,
+                                                  const uint8_t* __restrict__ err8, const uint8_t* __restrict__ blk,
+                                                  const uint8_t* __restrict__ m, const uint32_t* __restrict__ best,
+                                                  uint32_t* __restrict__ mate, unsigned long long* __restrict__ key,
+                                                  uint32_t* __restrict__ ties) {
+    const HitAt at{h};
+    const ErrAt errAt{err8}, blockAt{blk};
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x - lane); base < n; base += stride) {
+        const uint64_t i = base + lane;
+        uint32_t pair = 0xFFFFFFFFu, tie = 0;  // tie: 1 for an even qid with m == s1, 1 << 16 for an odd one
+        unsigned long long k = kLinkNoKey;
+        if (i < n && flag[i] != 0) {  // kept: it has a score, so its partner's segment lies in the batch
+            const sahara_hit x = h[i];
+            const uint64_t q = x.qid - qidBase, p = pairPartner(x.qid) - qidBase;
+            if (q < nq && p < nq) {
+                pair = (uint32_t)(q >> 2);
+                const uint64_t last = min(qoff[p + 1], n), first = min(qoff[p], last);
+                const BestRange r = bestMateRange(at, x.qid, x.seq_id, x.pos, dmin, dmax, first, last);
+                const uint32_t score = m[i];
+                const uint64_t j = bestRangeArgMin(errAt, blockAt, r.lb, r.ub, score - min(x.err, kBestNone - 1u));
+                mate[i] = j < r.ub ? (uint32_t)j : (uint32_t)i;  // (always j < ub: m[i] was made from this range's least)
+                const bool odd = (x.qid & 1ull) != 0;
+                if (!odd) k = pairPrimaryKey(score, (uint32_t)i);
+                if (score == best[pair]) tie = odd ? 1u << 16 : 1u;
+            }
+        }
+        const RunEnds r = runEnds(pair, lane);
+#pragma unroll
+        for (uint32_t off = 1; off < 64; off <<= 1) {
+            const unsigned long long ok = __shfl_up(k, off);
+            const uint32_t ot = __shfl_up(tie, off);
+            if (lane >= r.first + off) {
+                k = ok < k ? ok : k;
+                tie += ot;  // (at most 64 in either half)
+            }
+        }
+        if (r.last && pair != 0xFFFFFFFFu) {
+            if (k != kLinkNoKey) atomicMin(key + pair, k);
+            if (tie & 0xFFFFu) atomicAdd(ties + 2 * (uint64_t)pair, tie & 0xFFFFu);
+            if (tie >> 16) atomicAdd(ties + 2 * (uint64_t)pair + 1, tie >> 16);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void kLinkWrite(const sahara_hit* __restrict__ h, uint64_t n, uint64_t qidBase,
+                                                  uint32_t nq, const uint32_t* __restrict__ flag,
+                                                  const uint32_t* __restrict__ num, const uint32_t* __restrict__ mate,
+                                                  const uint8_t* __restrict__ m, const uint32_t* __restrict__ best,
+                                                  const uint32_t* __restrict__ next,
+                                                  const unsigned long long* __restrict__ key,
+                                                  const uint32_t* __restrict__ ties, uint64_t kept,
+                                                  sahara_pair_link* __restrict__ link) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x - lane); base < n; base += stride) {
+        const uint64_t i = base + lane;
+        if (i >= n || flag[i] == 0) continue;  // (no wave-wide step below: a lane may sit an iteration out)
+        const uint64_t qid = h[i].qid, q = qid - qidBase;
+        const uint32_t self = num[i] - 1u;
+        if (q >= nq || self >= kept) continue;
+        const uint32_t pair = (uint32_t)(q >> 2), j = mate[i];  // (j < n: kLinkMates wrote a row of the batch)
+        const unsigned long long k = key[pair];
+        bool primary = false;
+        if (k != kLinkNoKey) {
+            const uint32_t ki = pairPrimaryIndex(k);  // (a row of the batch as well, and kept: mate[ki] is written)
+            primary = (qid & 1ull) == 0 ? ki == (uint32_t)i : mate[ki] == (uint32_t)i;
+        }
+        sahara_pair_link x;
+        x.mate = (int32_t)((num[j] - 1u) - self);
+        x.score = m[i];
+        x.mapq = primary ? (uint8_t)pairMapq(best[pair], next[pair], max(ties[2 * (uint64_t)pair], ties[2 * (uint64_t)pair + 1])) : 0;
+        x.flags = primary ? kLinkPrimary : 0;
+        x.reserved = 0;
+        link[self] = x;
+    }
+}
+
+// The pinned links grown to hold `need`, the first `keep` kept: the copies of the earlier batches, all on
+// st, are waited for first. Grown by half again, so that a call of many batches allocates a few times.
+void growLinks(PinnedBuf<sahara_pair_link>& buf, uint64_t need, uint64_t keep, hipStream_t st) {
+    if (need <= buf.cap) return;
+    SH_HIP(hipStreamSynchronize(st));
+    PinnedBuf<sahara_pair_link> grown;
+    grown.reserve(std::max<uint64_t>(need + need / 2, 1024));
+    if (keep) std::copy_n(buf.ptr, keep, grown.ptr);
+    buf = std::move(grown);
+}
+
 }  // namespace
 
 // flag[i] = record i of the batch has a concordant mate in it (kPairFlags): the pair stage's first
@@ -281,7 +401,9 @@ void launchPairFlags(const BatchView& v, uint64_t dmin, uint64_t dmax, uint32_t*
 // last copy: the caller reads it after the batch's chain. best != nullptr:
 // best mode, which keeps of those hits each pair's least-error placements
 // (within best->delta) and copies the batch's pair summaries to
-// best->summary[q0 / 4 ..] (pinned, read after the batch's chain as well).
+// best->summary[q0 / 4 ..] (pinned, read after the batch's chain as well);
+// best->links != nullptr: and the kept records' links to the call's links
+// from best->links->at on (pinned too, grown here once the count is known).
 void pairsBatch(BatchView& v, uint32_t len, uint32_t minFrag, uint32_t maxFrag, PairsBufs& B, uint64_t* hostPairs,
                 const BestPairsIn* best) {
     *hostPairs = 0;
@@ -321,6 +443,32 @@ void pairsBatch(BatchView& v, uint32_t len, uint32_t minFrag, uint32_t maxFrag, 
                            B.best.ptr + npairs, B.sum.ptr);
         SH_HIP(hipGetLastError());
         SH_HIP(hipMemcpyAsync(best->summary + v.q0 / 4, B.sum.ptr, (size_t)npairs * sizeof(sahara_pair_summary),
+                              hipMemcpyDeviceToHost, v.st));
+    }
+    B.linkTimed = false;
+    if (best && best->links && kept) {  // the kept records' links, while the flags, the scores and the old rows stand
+        room(B.mate, rows);
+        room(B.key, npairs);
+        room(B.ties, 2 * (uint64_t)npairs);
+        room(B.link, kept);
+        if (!B.linkStart.e) {
+            B.linkStart = Event(hipEventDefault);
+            B.linkDone = Event(hipEventDefault);
+        }
+        SH_HIP(hipMemsetAsync(B.key.ptr, 0xFF, (size_t)npairs * sizeof(unsigned long long), v.st));
+        SH_HIP(hipMemsetAsync(B.ties.ptr, 0, 2 * (size_t)npairs * sizeof(uint32_t), v.st));
+        SH_HIP(hipEventRecord(B.linkStart, v.st));
+        hipLaunchKernelGGL(kLinkMates, dim3(blocks), dim3(256), 0, v.st, v.hits, rows, d.dmin, d.dmax, v.qoff, v.q0, v.nq,
+                           B.flag.ptr, B.err8.ptr, B.blk.ptr, B.score.ptr, B.best.ptr, B.mate.ptr, B.key.ptr, B.ties.ptr);
+        SH_HIP(hipGetLastError());
+        hipLaunchKernelGGL(kLinkWrite, dim3(blocks), dim3(256), 0, v.st, v.hits, rows, v.q0, v.nq, B.flag.ptr, B.num.ptr,
+                           B.mate.ptr, B.score.ptr, B.best.ptr, B.best.ptr + npairs, B.key.ptr, B.ties.ptr, kept,
+                           B.link.ptr);
+        SH_HIP(hipGetLastError());
+        SH_HIP(hipEventRecord(B.linkDone, v.st));
+        B.linkTimed = true;
+        growLinks(*best->links->buf, best->links->at + kept, best->links->at, v.st);
+        SH_HIP(hipMemcpyAsync(best->links->buf->ptr + best->links->at, B.link.ptr, (size_t)kept * sizeof(sahara_pair_link),
                               hipMemcpyDeviceToHost, v.st));
     }
     if (kept == 0) {  // (no rows: no later stage runs on them, nothing reads the segments)

@@ -58,6 +58,8 @@ void checkPairsCall(const Ctx* c, uint64_t npat, uint32_t len) {
                             " starts is above SAHARA_RESCUE_MAX_WINDOW (" + std::to_string(kRescueMaxWindow) + ")");
         }
     }
+    if (c->pairs.links && !c->pairs.best)  // (docs/semantics.md "Pair links", refused calls)
+        throw Error("pair links: needs best pairs on (a link is a record of the best-pairs rule)");
     if (c->pairs.best) {  // (docs/semantics.md "Best pairs", refused calls)
         if (!c->pairs.on) throw Error("best pairs: needs pairs on (the placements ranked are the pair rule's)");
         if (!c->more.empty())
@@ -81,6 +83,11 @@ void run(Ctx* c, bool count) {
     c->pairs.summaryOn = c->sk.staged && c->pairs.on && c->pairs.best;
     c->pairs.summaryPairs = c->pairs.summaryOn ? c->npat / 4 : 0;
     if (c->pairs.summaryOn) c->pairs.summary.reserve(std::max<uint64_t>(c->pairs.summaryPairs, 1));
+    // pair links: one per hit of the call, written per batch from c->nout on; --max_hits would cut linked hits
+    if (c->sk.staged && c->pairs.links && c->sk.limitN)
+        throw Error("pair links: a call with max_hits is not supported (the cut would drop linked hits)");
+    c->pairs.linksOn = c->pairs.summaryOn && c->pairs.links;
+    c->pairs.linkCount = 0;
     if (c->more.empty()) return runOne(c, count);
     // (rounds mask a query by its rows in one part; "found" is decided across the parts: capi.cpp bestOnHost)
     if (c->rounds.size() > 1) throw Error("a pass of several rounds needs a single-part index");
@@ -151,6 +158,7 @@ void runOne(Ctx* c, bool count) {
     S.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     S.stage_ms = c->stageMs;
     c->stats = S;
+    if (c->pairs.linksOn) c->pairs.linkCount = c->nout;  // (one part: the pass's hits are the call's)
 }
 
 const sahara_hit* Ctx::wholeHits() {
@@ -780,7 +788,8 @@ struct Pass {
                 // docs/semantics.md "Pairs": the hits with a mate in the batch, which holds whole pairs; in
                 // best mode ("Best pairs") of those each pair's least-error placements, and `kept` counts
                 // what leaves the stage either way
-                const BestPairsIn best{c->pairs.delta, c->pairs.summary.ptr};
+                const PairLinksOut links{&c->pairs.linkBuf, c->nout};
+                const BestPairsIn best{c->pairs.delta, c->pairs.summary.ptr, c->pairs.linksOn ? &links : nullptr};
                 T.pairs.hits_in += v.rows;
                 pairsBatch(v, c->m, c->pairs.minFrag, c->pairs.maxFrag, c->pairs.bufs, &rec.pairs,
                            c->pairs.summaryOn ? &best : nullptr);
@@ -861,6 +870,10 @@ struct Pass {
             *total += ms;
             // (flagsDown has passed the pair stage's last copy, the one into the batch's record)
             if (s == kStagePairs) c->stageStats.pairs.pairs += c->pinned.ptr[b].pairs;
+            if (s == kStagePairs && c->pairs.linksOn && c->pairs.bufs.linkTimed) {
+                SH_HIP(hipEventElapsedTime(&ms, c->pairs.bufs.linkStart, c->pairs.bufs.linkDone));
+                c->stageStats.linkMs += ms;
+            }
         }
         c->mark("checked", b);
     }

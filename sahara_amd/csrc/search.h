@@ -340,12 +340,25 @@ struct PairsBufs {
     DevBuf<uint8_t> err8, blk, score;   // per record: its err; per aligned 64 records: their least err; per record: m
     DevBuf<uint32_t> best;              // per pair of the batch: s1, then (a second array behind it) next
     DevBuf<sahara_pair_summary> sum;    // per pair of the batch: its summary, copied to the host per batch
+    // links (docs/semantics.md "Pair links"):
+    DevBuf<uint32_t> mate, ties;        // per kept record: its mate's row; per pair: its even, then odd records with m == s1
+    DevBuf<unsigned long long> key;     // per pair: the least primary key (pair_links_core.h)
+    DevBuf<sahara_pair_link> link;      // per record that leaves: its link, copied to the host per batch
+    Event linkStart, linkDone;          // around the two link kernels of the last batch ...
+    bool linkTimed = false;             // ... if they ran on it (a batch that keeps nothing runs none)
+};
+// The call's links in pinned host memory, hit 0 of the call first: a batch's go to buf[at ..), and buf
+// grows to hold them with what lies before `at` kept (the earlier batches')
+struct PairLinksOut {
+    PinnedBuf<sahara_pair_link>* buf;
+    uint64_t at;
 };
 // best mode of the pair stage: the slack, and the call's pair summaries in pinned host memory (pair 0 of the
 // call first; a batch writes its pairs' from q0 / 4 on)
 struct BestPairsIn {
     uint32_t delta;
     sahara_pair_summary* summary;
+    const PairLinksOut* links;  // nullptr: no links
 };
 // *hostPairs (pinned) gets the pairs with a kept hit once v.st has passed the call; best: nullptr = off
 void pairsBatch(BatchView& v, uint32_t len, uint32_t minFrag, uint32_t maxFrag, PairsBufs& B, uint64_t* hostPairs,
