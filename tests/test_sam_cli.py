@@ -2,19 +2,23 @@
 tests/best_pairs_case.py, its records and reads written as FASTA: the file is
 tests/sam_model.py's text byte for byte (the model's rows, links and
 alignments), two shards write the same bytes, the lines hold together as SAM
-whatever the model says, and the flag's refusals."""
+whatever the model says, and the flag's refusals; and with --rescue on the
+widest-window point of tests/paired_grid_case.py (dna4, patterns of 33
+symbols): the alignment bound is max(-e, --rescue)."""
 import functools
 import re
 
 import numpy as np
 import pytest
 
+import paired_grid_case as grid
 from best_pairs_case import K, M, SIGMA, WIDE, planted
 from loci_model import loci
 from pair_links_case import check, expected_links
 from pair_links_model import pair_links
 from sam_model import sam_text
 from test_cli import run
+from test_golden import CHARS
 from test_multi_device import _env, run_env
 from test_pairs_cli import write_fasta
 
@@ -61,8 +65,8 @@ def cigar_lengths(cigar):
     return (sum(int(n) for n, o in ops if o in "=XI"), sum(int(n) for n, o in ops if o in "=XD"))
 
 
-def check_structure(text, n_pairs, n_records):
-    """What holds of the file as SAM, whatever the model says."""
+def check_structure(text, n_pairs, n_records, length):
+    """What holds of the file as SAM, whatever the model says; length: the reads'."""
     lines = text.splitlines()
     head = [ln for ln in lines if ln.startswith("@")]
     body = lines[len(head):]
@@ -80,7 +84,7 @@ def check_structure(text, n_pairs, n_records):
         if fs[0][2] == "*":  # unmapped: the two reads, flags 77 and 141
             assert [f[1] for f in fs] == ["77", "141"], P
             for f in fs:
-                assert f[2:9] == ["*", "0", "0", "*", "*", "0", "0"] and len(f[9]) == M and f[10] == "*" and len(f) == 11
+                assert f[2:9] == ["*", "0", "0", "*", "*", "0", "0"] and len(f[9]) == length and f[10] == "*" and len(f) == 11
             continue
         mapped += 1
         prim = {0x40: [], 0x80: []}
@@ -89,7 +93,7 @@ def check_structure(text, n_pairs, n_records):
             assert len(f) == 13 and flag & 0x3 == 0x3 and bool(flag & 0x10) != bool(flag & 0x20), f
             assert bool(flag & 0x40) != bool(flag & 0x80) and flag & ~0x1F3 == 0, f
             qlen, rlen = cigar_lengths(f[5])
-            assert qlen == len(f[9]) == M and set(f[9]) <= set("ACGTN"), f
+            assert qlen == len(f[9]) == length and set(f[9]) <= set("ACGTN"), f
             assert f[6] == "=" and f[10] == "*" and re.fullmatch(r"NM:i:\d+", f[11]) and re.fullmatch(r"ZP:i:\d+", f[12])
             assert 0 <= int(f[4]) <= 60 and (int(f[4]) == 0 or not flag & 0x100), f
             assert abs(int(f[8])) >= rlen, f
@@ -114,7 +118,7 @@ def test_sam_is_the_models_text(files, delta):
     mapq30 = int(((links["flags"] & 1 != 0) & (links["mapq"] >= 30)).sum()) // 2
     assert links_line(so) == (len(links), n_prim, mapq30)
     assert "  align time:" in so and f"  number of hits:      {len(links):>10}" in so
-    assert check_structure(text, c["n_pairs"], len(c["recs"])) == n_prim // 2
+    assert check_structure(text, c["n_pairs"], len(c["recs"]), M) == n_prim // 2
     assert 0 < n_prim // 2 < c["n_pairs"]  # (the case has pairs that keep nothing)
     # without the flag the run is what it was: the hit lines, no links line
     so, plain = search(files, "plain.txt", *FRAG, *(f for f in flags if f != "--sam"), "--emit-errors")
@@ -126,7 +130,7 @@ def test_sam_with_loci(files):
     want, links = model_text(0, 2)
     so, text = search(files, "loci.sam", *FRAG, "--best-pairs", "--sam", "--loci-window", 2)
     assert text == want != model_text(0)[0]
-    check_structure(text, c["n_pairs"], len(c["recs"]))
+    check_structure(text, c["n_pairs"], len(c["recs"]), M)
 
 
 def test_two_shards_write_the_same_bytes(files):
@@ -135,6 +139,42 @@ def test_two_shards_write_the_same_bytes(files):
     so2, two = search(files, "two.sam", *FRAG, "--best-pairs", "--sam", "--gpus", 2, env=_env(2))
     assert one == two == model_text(0)[0]
     assert links_line(so1) == links_line(so2) and so2.count("  device ") == 2
+
+
+def write_fasta_of(path, rows, name, sigma):
+    letters = np.frombuffer(CHARS[sigma].encode(), np.uint8)
+    with open(path, "w") as f:
+        for i, r in enumerate(rows):
+            f.write(f">{name}{i}\n{letters[np.asarray(r)].tobytes().decode()}\n")
+    return str(path)
+
+
+def test_sam_with_rescue(tmp_path, gpu_device):
+    """--rescue with --sam on a dna4 index: rescued records carry up to --rescue
+    errors, above -e's, and are aligned with the larger bound; records of one
+    symbol and the widest fragment window come through the command line."""
+    point = grid.WIDEST
+    c = grid.check(point)
+    kept, summary, links, info = grid.links(point, 0)
+    want = sam_text(c["recs"], c["pats"], point.sigma, kept, links, c["n_pairs"], max(point.K, point.Kr))
+    ref = write_fasta_of(tmp_path / "ref.fa", c["recs"], "rec", point.sigma)
+    rc, _, err = run("index", ref, "--dna4")
+    assert rc == 0, err
+    out = tmp_path / "rescue.sam"
+    rc, so, err = run("search", "-q", write_fasta_of(tmp_path / "reads.fa", c["reads"], "read", point.sigma), "-i",
+                      ref + ".dna4.idx", "-o", out, "-e", point.K, "-g", point.generator, "--paired", "--min-fragment",
+                      point.frag[0], "--max-fragment", point.frag[1], "--rescue", point.Kr, "--rescue-anchors", 0,
+                      "--best-pairs", "--sam")
+    assert rc == 0, err
+    text = out.read_text()
+    assert text == want
+    n_prim = int((links["flags"] & 1).sum())
+    mapq30 = int(((links["flags"] & 1 != 0) & (links["mapq"] >= 30)).sum()) // 2
+    assert links_line(so) == (len(links), n_prim, mapq30)
+    assert check_structure(text, c["n_pairs"], len(c["recs"]), point.M) == n_prim // 2
+    # rescued records are in the file: lines with more errors than -e allows, up to --rescue's
+    nm = [int(x) for x in re.findall(r"\tNM:i:(\d+)\t", text)]
+    assert len(nm) == len(kept) and max(nm) == point.Kr > point.K and sum(1 for x in nm if x > point.K) >= 20
 
 
 def test_refusals(files):
