@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../csrc/fasta.h"
+#include "options.h"
 
 namespace sahara_cli {
 using namespace sahara_io;
@@ -123,13 +124,6 @@ void writeRecord(std::FILE* f, const std::string& id, const std::string& seq, si
 }
 
 }  // namespace
-
-struct ReadSimulatorArgs {  // mirrored in main.cpp
-    std::string input, output;
-    size_t lineLength = 80, readLength = 150, nreads = 1000, sub = 0, ins = 0, del = 0, errors = 0;
-    uint32_t seed = 0;
-    bool haveInput = false;
-};
 
 int runReadSimulator(const ReadSimulatorArgs& a) {
     std::srand(a.seed);

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/sahara_hip.h"
+#include "compact_hit.h"
 #include "device_index.h"
 #include "hit_route.h"
 #include "host_pool.h"
@@ -119,20 +120,14 @@ private:
         const uint64_t per = (j.n + nt - 1) / nt;
         pool_.run([&](unsigned t) {
             const uint64_t b = std::min(j.n, (uint64_t)t * per), e = std::min(j.n, b + per);
-            uint32_t seq = 0;
-            uint64_t lo = 1, hi = 0;  // the current record's [start, next start): empty
+            sahara_compact::RecordCursor rec(S.data(), S.size());
             for (uint64_t i = b; i < e; ++i) {
-                const uint64_t v = j.src[i], g = (v >> 4) & 0xFFFFFFFFull;
-                if (g < lo || g >= hi) {  // hits come sorted by (qid, seq_id, pos): mostly the same record
-                    seq = (uint32_t)(std::upper_bound(S.begin(), S.end(), g) - S.begin() - 1);
-                    lo = S[seq];
-                    hi = seq + 1 < S.size() ? S[seq + 1] : UINT64_MAX;
-                }
+                const uint64_t v = j.src[i];
                 sahara_hit& h = j.dst[i];
-                h.qid = j.q0 + (v >> 36);
-                h.seq_id = seq;
-                h.err = (uint32_t)(v & 15u);
-                h.pos = g - lo;
+                h.pos = rec.seek(sahara_compact::textOf(v));
+                h.qid = j.q0 + sahara_compact::qidOf(v);
+                h.seq_id = (uint32_t)rec.seq;
+                h.err = sahara_compact::errOf(v);
             }
         });
     }

@@ -117,6 +117,59 @@ def test_search_bad_enum_values():
     assert run(*base, "-d", "hamming")[0] == 1
 
 
+SAM_NEEDS = ("--sam needs --paired --best-pairs (a SAM record names its mate, and a pair's primary placement and MAPQ "
+             "come from the best-pairs rule)")
+NEED_BEST = "--pair-delta / --pair-summary need --best-pairs"
+# What the command line alone refuses, and the message, pinned literally. The index path does not exist: a
+# flag error wins over "no valid index path".
+REFUSALS = [
+    (["--min-fragment", 10], "--min-fragment / --max-fragment need --paired"),
+    (["--max-fragment", 10], "--min-fragment / --max-fragment need --paired"),
+    (["--paired", "--no-reverse"], "--paired needs the reverse complements: it cannot go with --no-reverse"),
+    (["--paired", "--min-fragment", 600], "--min-fragment is above --max-fragment"),
+    (["--paired", "--max-fragment", 2**32], "--max-fragment is at most 4294967295"),
+    (["--paired", "--limit_queries", 6],
+     "--paired: --limit_queries must be a multiple of 4 (a pair is two mates and their reverse complements)"),
+    (["--paired", "--limit_queries", "abc"], "invalid value for --limit_queries: abc"),
+    (["--sam"], SAM_NEEDS),
+    (["--paired", "--sam"], SAM_NEEDS),
+    (["--best-pairs", "--sam"], SAM_NEEDS),
+    (["--paired", "--best-pairs", "--sam", "--max_hits", 3],
+     "--sam cannot go with --max_hits (the cut would drop linked hits)"),
+    (["--emit-cigar", "-e", 9], "--emit-cigar aligns at most 8 errors (-e)"),
+    (["--paired", "--best-pairs", "--sam", "-e", 9], "--sam aligns at most 8 errors (-e)"),
+    (["--rescue-anchors", 3], "--rescue-anchors needs --rescue"),
+    (["--rescue", 2], "--rescue needs --paired (a mate is looked for in the fragment window)"),
+    (["--paired", "--rescue", 0], "--rescue takes 1 to 8 errors"),
+    (["--paired", "--rescue", 9], "--rescue takes 1 to 8 errors"),
+    (["--paired", "--rescue", 2, "--rescue-anchors", 2**32], "--rescue-anchors is at most 4294967295"),
+    (["--pair-delta", 1], NEED_BEST),
+    (["--pair-summary", "s.txt"], NEED_BEST),
+    (["--paired", "--pair-delta", 1], NEED_BEST),
+    (["--best-pairs"], "--best-pairs needs --paired (the placements ranked are pairs')"),
+    (["--paired", "--best-pairs", "--pair-delta", 31], "--pair-delta is at most 30"),
+    (["--loci-window", 2**32], "--loci-window is at most 4294967295"),
+    (["--loci-window", "w"], "invalid value for --loci-window: w"),
+    (["--frobnicate"], "unknown option --frobnicate"),
+    (["stray"], "unexpected argument stray"),
+    (["-e", "two"], "invalid value for --errors: two"),
+    (["--gpus", "x"], "invalid value for --gpus: x"),
+    (["--limit_queries"], "option --limit_queries expects a value"),
+    (["-m", "fast"], "invalid value for --search_mode: fast"),
+    (["-d", "hamming"], "invalid value for --distance-metric: hamming"),
+    # two errors that wait for the index, which therefore wins
+    (["--limit_queries", "abc"], "no valid index path at {index}"),
+    ([], "no valid index path at {index}"),
+]
+
+
+@pytest.mark.parametrize("args,message", REFUSALS, ids=[" ".join(map(str, a)) or "none" for a, _ in REFUSALS])
+def test_search_refusals_need_no_index(args, message, tmp_path):
+    index = tmp_path / "none.idx"
+    rc, out, err = run("search", "-q", tmp_path / "reads.fa", "-i", index, *args)
+    assert (rc, out, err) == (1, "", message.format(index=index) + "\n")
+
+
 # ------------------------------------------------------------------ GPU ----
 
 def cli_args(c):
